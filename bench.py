@@ -13,9 +13,13 @@ g = p mod G (src/log_utilities.erl:65-70); with G | 64 each rank owns keys
 k = rank + G*i, i < keys_per_gpu.  Materialize has no collective.
 
 Default (no flags): N=1, BASELINE cfg2 = counter_pn, 10M keys x 64 ops/key,
-8-DC clocks, random snapshot VCs.
+8-DC clocks, random snapshot VCs.  A plain run sets up, warms up, times the K
+steps and prints the result line; --full adds everything else the default
+run reports (CPU baselines, the HBM read probe, the other BASELINE configs
+as sub-lines, the detail file).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -61,8 +65,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--keys", type=int, default=0, help="override keys per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines, the "
+                         "HBM read probe, the 'auto' sub-configs (--configs) and the detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's results as DIR/<name>.npy "
+                         "(float64; a fixed seeded sample of the requests above 64 MB)")
     ap.add_argument("--cpu-keys", type=int, default=-1,
-                    help="CPU-baseline sample size in keys (0 = skip)")
+                    help="CPU-baseline sample size in keys (0 = skip; default: sized by the "
+                         "config with --full, skipped without)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="extra multi-thread CPU run")
     ap.add_argument("--tune-rounds", type=int, default=3,
                     help="agn_tune launches per kernel variant before timing (0 = no tuning)")
@@ -92,8 +103,9 @@ def parse():
                          "line's 'configs' object: comma list of 1, 2:full, 2:mixed, 3, 4, 5, "
                          "N:warm (read/6 from the device snapshot cache: lookup -> warm "
                          "materialize -> store), N:gc (the one-pass prune_ops GC); "
-                         "'auto' = " + AUTO_CONFIGS + " (N = 1) or the multi-GPU ones 4, 5 "
-                         "(N > 1) when the headline is the default cfg2 run; 'none' = headline only")
+                         "'auto' = with --full, " + AUTO_CONFIGS + " (N = 1) or the multi-GPU ones "
+                         "4, 5 (N > 1) when the headline is the default cfg2 run; 'none' = headline "
+                         "only")
     ap.add_argument("--cpu-target-s", type=float, default=10.0,
                     help="seconds of CPU work per thread count in the CPU baseline")
     return ap.parse_args()
@@ -408,6 +420,7 @@ def main():
     for name, cid, sparse, mode in sub_configs(a, world):
         sa = argparse.Namespace(**vars(a))
         sa.config, sa.sparse, sa.keys, sa.configs = cid, sparse, 0, "none"
+        sa.dump_outputs = None
         sa.gc = sa.warm = sa.ingest = sa.e2e = sa.gst = sa.post_gc = False
         # a warm / gc sub-line reports that path as its own line (line_mode)
         sa.line_mode = mode
@@ -423,7 +436,7 @@ def main():
     if rank == 0:
         if configs:
             line["configs"] = configs
-        detail = write_detail(line)
+        detail = write_detail(line) if a.full else None
         print(json.dumps(compact_line(line, detail)), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -519,6 +532,8 @@ def sub_configs(a, world):
     "N:full|mixed|subsetK" = presence masks, "N:warm" / "N:gc" = that path."""
     spec = a.configs
     if spec == "auto":
+        if not a.full:
+            return []
         extra = a.gc or a.warm or a.ingest or a.e2e or a.post_gc or a.gst or a.keys
         if a.config != 2 or a.sparse or extra:
             return []
@@ -663,7 +678,11 @@ def materialize_main(a, torch, dist, world, rank, local, backend):
     bytes_survey = algorithmic_bytes_survey(cfg, n_keys, n_rem, n_live)
     achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
 
-    probe = probe_read_gbs(eng, dl, n_keys * cfg["ops_per_key"] * cfg["n_dcs"] * 8, sp, torch)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, result_arrays(eng, res, cfg, n_keys))
+
+    probe = probe_read_gbs(eng, dl, n_keys * cfg["ops_per_key"] * cfg["n_dcs"] * 8, sp, torch) \
+        if a.full else None
 
     gc = gc_bench(eng, dl, dr, cfg, n_keys, sp, torch, a.config) if a.gc else None
     warm = warm_bench(eng, dl, dr, cfg, n_keys, sp, torch, a.steps, a.config) if a.warm else None
@@ -682,7 +701,7 @@ def materialize_main(a, torch, dist, world, rank, local, backend):
         cpu = None
         # ~64M ops of host-generated sample (8M for a sub-config), timed for
         # ~cpu_target_s seconds per thread count
-        n_cpu = a.cpu_keys if a.cpu_keys >= 0 else \
+        n_cpu = a.cpu_keys if a.cpu_keys >= 0 else 0 if not a.full else \
             (64_000_000 if a.cpu_keys == -1 else 8_000_000) // cfg["ops_per_key"]
         mode = getattr(a, "line_mode", "")
         if world == 1 and n_cpu > 0 and mode == "gc":
@@ -781,6 +800,49 @@ def materialize_main(a, torch, dist, world, rank, local, backend):
     eng.close()
     torch.cuda.empty_cache()
     return line
+
+
+DUMP_MAX_BYTES = 60_000_000  # under 64 MB with room for the .npy headers
+DUMP_SEED = 20250112
+
+
+def result_arrays(eng, res, cfg, n_keys):
+    """What a caller of agn_materialize receives for the batch, one row per
+    request, with the fields the ABI leaves undefined zeroed (LastOpCt of a
+    request flagged AGN_F_CT_IGNORE, the error position of a request without
+    an error flag, the state slots past out_n): two builds that compute the
+    same results give the same arrays."""
+    from antidote_amd import _abi
+    get = {n: eng.download(res.bufs[n], *res.shapes[n]) for n in res.shapes if n != "out_off"}
+    flags = get["flags"]
+    get["lastct"][(flags & np.uint32(_abi.F_CT_IGNORE)) != 0] = 0
+    get["err_pos"][(flags & np.uint32(_abi.F_ERR_CORRUPTED | _abi.F_ERR_UNEXPECTED)) == 0] = 0
+    if cfg["crdt_type"] == 1:
+        return get
+    del get["value"]  # counter_pn's field
+    N = cfg["ops_per_key"]  # every request's state capacity (cap_off)
+    live = np.arange(N, dtype=np.uint32)[None, :] < get["out_n"][:, None]
+    for n in ("out_tag", "out_tok"):
+        get[n] = np.where(live, get[n].reshape(n_keys, N), 0)
+    return get
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (clocks and
+    tokens of the generators stay below 2^53).  Past DUMP_MAX_BYTES in all,
+    the same fraction of every array's rows: a fixed seeded sample, the same
+    row indices for every array of one length."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.size * 8 for a in arrays.values())
+    idx = {}
+    for name, arr in arrays.items():
+        n = arr.shape[0]
+        if total > DUMP_MAX_BYTES:
+            if n not in idx:
+                k = max(1, n * DUMP_MAX_BYTES // total)
+                idx[n] = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+            arr = arr[idx[n]]
+        np.save(os.path.join(dirpath, name + ".npy"), arr.astype(np.float64))
 
 
 def ingest_bench(eng, cfg, sp, torch, n_txn=10_000_000, n_keys=1_000_000):
@@ -1502,6 +1564,8 @@ def gst_main(a, torch, dist, world, rank, local, backend):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kern_ms = float(np.mean([b.elapsed_time(e) for b, e in evs]))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"gst": out.cpu().numpy()})
     if world > 1:
         t = torch.tensor([elapsed, kern_ms], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1560,7 +1624,7 @@ def gst_main(a, torch, dist, world, rank, local, backend):
     if rank == 0:
         traffic, traffic_src = pmc_traffic(5, Pl)
         cpu = None
-        if world == 1 and a.cpu_keys != 0:
+        if world == 1 and (a.cpu_keys > 0 or (a.full and a.cpu_keys != 0)):
             lib = _abi.bind(C.CDLL(os.path.join(ROOT, "oracle", "liboracle.so")),
                             _abi.ORACLE_PROTOTYPES)
             Es = 16

@@ -8,9 +8,9 @@
 # the script (no further GPU work after a fault, abort or time limit) and
 # prints the tail of its log.  Recipes used every round:
 #
-#   roundend  : the driver's tiers -- pytest -m gpu, smoke(), default bench
-#   trace     : rocprofv3 --kernel-trace --stats of the driver's exact bench
-#               command (profiles/rNN/kernel_stats_*.csv)
+#   roundend  : the driver's tiers -- pytest -m gpu, smoke(), bench.py --full
+#   trace     : rocprofv3 --kernel-trace --stats of the bench.py --full run
+#               (profiles/rNN/kernel_stats_*.csv)
 #   pmc       : FETCH_SIZE / WRITE_SIZE passes (one counter block per run)
 #   serve     : the native read/6 serving load generator (tools/serve_bench)
 #
@@ -18,6 +18,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+OUT=${PROF_OUT:-prof_out}   # where the trace recipe's profiler output goes
 : > gpurun_out/steps.txt
 
 run_step() {
@@ -48,9 +49,9 @@ expand() {
     roundend)
       echo "pytest_gpu|900|python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread"
       echo "smoke|200|python -u -c 'import __graft_entry__ as g; g.smoke()'"
-      echo "bench|400|python -u bench.py";;
+      echo "bench|400|python -u bench.py --full";;
     trace)
-      echo "trace|400|rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_trace -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5";;
+      echo "trace|400|rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5";;
     pmc)
       # one counter block per run (FETCH_SIZE, then WRITE_SIZE), per config
       for c in ${PMC_CONFIGS-1 2 3 4 5}; do

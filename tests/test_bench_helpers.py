@@ -78,7 +78,7 @@ def test_algorithmic_bytes_match_design():
 
 
 def test_final_line_fits_driver_tail():
-    """The default run's final stdout line, built from a recorded full line
+    """The --full run's final stdout line, built from a recorded full line
     (round 5's closing run: headline + nine sub-lines, 20.5 KB), stays under
     8000 bytes and keeps the headline's roofline / cpu_baseline whole and one
     summary per sub-config."""
@@ -107,6 +107,52 @@ def test_final_line_fits_driver_tail():
     big = dict(full, configs={f"c{i}": full["configs"]["cfg3_gc"] for i in range(60)})
     out = bench.compact_line(big)
     assert len(json.dumps(out)) < 8000 and out["roofline"]["frac"] == full["roofline"]["frac"]
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """Without --full the default run has no sub-configs (and the CPU
+    baseline's 'sized by the config' default stays off); --full brings the
+    'auto' set back, an explicit --configs list is honoured either way."""
+    def args(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+    a = args("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert bench.sub_configs(a, 1) == []
+    full = args("--full")
+    assert [n for n, *_ in bench.sub_configs(full, 1)] == [
+        "cfg1", "cfg2_masked_full", "cfg3", "cfg4", "cfg5", "cfg2_warm", "cfg3_warm", "cfg4_warm",
+        "cfg3_gc"]
+    assert [n for n, *_ in bench.sub_configs(full, 2)] == ["cfg4", "cfg5"]
+    assert [n for n, *_ in bench.sub_configs(args("--configs", "3,4:warm"), 1)] == \
+        ["cfg3", "cfg4_warm"]
+    assert bench.sub_configs(args("--full", "--configs", "none"), 1) == []
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files named after the arrays; past the byte
+    budget every array keeps the same seeded rows, the same ones on every
+    call, and the files stay under the budget."""
+    import numpy as np
+    n = 1000
+    arrays = {"value": np.arange(n, dtype=np.int64) - 500,
+              "lastct": np.arange(n * 8, dtype=np.uint64).reshape(n, 8),
+              "flags": np.arange(n, dtype=np.uint32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for name, arr in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, arr.astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8000)   # of 80000: one row in ten
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    rows = got["flags"].astype(np.int64)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0)
+    assert sum(g.nbytes for g in got.values()) <= 8000
+    for name, arr in arrays.items():
+        assert got[name].dtype == np.float64
+        assert np.array_equal(got[name], arr[rows].astype(np.float64))
+        assert np.array_equal(got[name], np.load(tmp_path / "b" / f"{name}.npy"))
 
 
 def test_final_line_keeps_the_exchange_check():
