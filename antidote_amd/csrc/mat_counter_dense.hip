@@ -712,7 +712,9 @@ __device__ __forceinline__ void q2_epilogue(const Q2Key &k, Q2Acc &s, uint32_t h
     if (k.id0 != AGN_ID0_NONE)
         hid = k.n ? (int64_t)((uint64_t)k.id0 + pos) : 0;
     else
-        hid = k.n ? (int64_t)__builtin_amdgcn_readfirstlane(ldc(op_id + uniform_u64(k.off + pos))) : 0;
+        // readfirstlane returns int: an id with bit 31 set must not sign-extend into the hole
+        hid = k.n ? (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
+                        (int)ldc(op_id + uniform_u64(k.off + pos))) : 0;
     const int64_t base = base_value ? (int64_t)uniform_u64((uint64_t)ldc(base_value + i)) : 0;
     const int64_t total = wave_sum_dpp(s.sum);
     const bool ct_ign = k.sct_ign && s.cnt == 0u;

@@ -79,6 +79,23 @@ extern "C" {
  * lastct_mask[i] is NOT written (the mask is the n_dcs low bits) */
 #define AGN_F_CT_FULL 0x20u
 
+/* ---- value domain ------------------------------------------------------
+ * What agn_log / agn_read fields may hold; every kernel is tested bit-exact
+ * against the oracle over all of it (tests/test_value_domain.py):
+ *   clock entries (oc, R, sct, snapshot-cache clocks, GC thresholds, the rows
+ *     of agn_select_base / agn_dep_check / agn_gst_*): a PRESENT entry is any
+ *     u64 <= 2^64 - 2, 0 included; they are compared unsigned.  UINT64_MAX is
+ *     the "absent" sentinel of the GST path.  An absent column (mask bit 0)
+ *     may hold anything; a DC absent from SCT reads 0 (vectorclock 0.1.0).
+ *   eff / base_value: any i64 but INT64_MIN (AGN_EFFECT_INVALID, reserved);
+ *     the counter value is base + included effects mod 2^64, as int64.
+ *   add_tok / rem_tok / base_tok: any non-zero u64, 2^64 - 1 included; 0 in
+ *     add_tok means "none" (a remove / reset entry).
+ *   tag / base_tag: any u32 but 0xFFFFFFFF (AGN_TAG_INVALID, reserved).
+ *   op_id: any u32 but 0xFFFFFFFF (AGN_ID0_NONE, reserved by the id index);
+ *     `hole` is the id zero-extended to int64, or id - 1.
+ *   txid: any non-zero u64; 0 means "none" in the log and in a read. */
+
 /* ---- op log (device or host pointers, same layout) -------------------- */
 typedef struct agn_log {
     uint32_t crdt_type;       /* AGN_COUNTER_PN / AGN_SET_AW / AGN_REGISTER_MV */
