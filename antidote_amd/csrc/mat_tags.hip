@@ -632,7 +632,9 @@ __global__ __launch_bounds__(64 * WPB) void k_tags(agn_log log, agn_read req, ag
 
         // ---- live state -> sorted pairs
         uint32_t n_live = 0;
-        bool cap_err = overflow;
+        // an {error,..} found after the table overflowed is the read's only
+        // outcome (the fold fails before any state exists to overflow)
+        bool cap_err = overflow && first_err < 0;
         const uint64_t o = out.out_off[i];
         if (!overflow && first_err < 0) {
             n_live = compact<CAP>(L, used, false);

@@ -73,6 +73,15 @@ extern "C" {
 #define AGN_F_CT_IGNORE 0x2u      /* LastOpCt == ignore (nothing included, SCT ignore) */
 #define AGN_F_ERR_UNEXPECTED 0x4u /* {error,{unexpected_operation,Op,Type}}      */
 #define AGN_F_ERR_CORRUPTED 0x8u  /* erlang:error(corrupted_ops_cache)           */
+/* AGN_F_ERR_CAPACITY (set_aw / register_mv) has two causes; with either, the
+ * request's out_tag / out_tok range is not written and hole, count, lastct
+ * (+ mask), err_pos and the other flags are those of the read without the limit:
+ *   - the state does not fit the caller's room out_off[i+1] - out_off[i]:
+ *     out_n[i] is the state's size (the room to come back with);
+ *   - the key needs more than 4096 candidate pairs at once in the engine's
+ *     per-key table (live pairs plus a chunk's adds: the engine's own limit,
+ *     whatever room the caller gave): out_n[i] is 0.
+ * A request that ends in AGN_F_ERR_UNEXPECTED carries that error alone. */
 #define AGN_F_ERR_CAPACITY 0x10u  /* a per-key device table overflowed            */
 /* ABI v5: LastOpCt carries every column of the partition (its dict has all n_dcs
  * DCs); set only for requests of a batch with AGN_HINT_CT_FLAG, and then
