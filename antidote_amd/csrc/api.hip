@@ -721,6 +721,8 @@ int agn_log_ingest(agn_ctx *ctx, const agn_log_records *recs, uint32_t crdt_type
     out->key_id0 = nullptr;  // fresh op ids: no index until agn_log_index_ids
     if (recs->n == 0) {
         AGN_HIP(hipMemsetAsync((void *)out->key_off, 0, (n_keys + 1) * 8, (hipStream_t)stream));
+        if (o.rem_off)  // rem_off[n_entries] = 0 tokens, as for any other log
+            AGN_HIP(hipMemsetAsync((void *)o.rem_off, 0, sizeof(uint32_t), (hipStream_t)stream));
         if (out_totals) AGN_HIP(hipMemsetAsync(out_totals, 0, 16, (hipStream_t)stream));
         return AGN_OK;
     }

@@ -6,10 +6,18 @@
 //
 // The sequential walk "buffer updates per TxId, emit them at the commit
 // record" becomes a hash join + a stable sort:
-//   1. k_commit_map  every commit record inserts txid -> record index into an
-//                    open-addressing table (one commit per transaction);
-//   2. k_join        every update record looks up its transaction's commit c;
-//                    it is emitted iff c comes later in the log and
+//   1. k_commit_map  every commit record takes a slot of its own in an
+//                    open-addressing table keyed by its txid and stores
+//                    {txid, record index} there; it counts the records that
+//                    met an earlier claim of their own txid on the way (a
+//                    transaction id with more than one commit record);
+//   2. k_join        every update record looks up the first commit record c
+//                    of its txid that comes later in the log (handle_commit
+//                    erases the transaction: a later update of the same txid
+//                    waits for the next commit record) -- the first match of
+//                    its probe when no txid has two commit records, else the
+//                    smallest later match of its whole cluster; it is emitted
+//                    iff there is one and
 //                    check_max_time(snapshot_time(c), Max[key]) holds; its
 //                    sort key is (key << pb) | c with pb = the bits of a
 //                    record index (else n_keys << pb, after every key);
@@ -40,11 +48,12 @@ __device__ __forceinline__ uint64_t slot_of(uint64_t t, uint64_t mask) {
     return (t * 0x9E3779B97F4A7C15ull) >> 20 & mask;
 }
 
-// The commit table: open addressing over {txid, first commit index} slot
-// pairs (one 16-byte access per probe), sized on the device from the number
-// of commit records (a power of two >= 1.5x, so a log of 10M commits probes a
-// 256 MiB table that the MALL can hold) -- tab[0] of the scratch holds the
-// mask, the slots follow.
+// The commit table: open addressing over {txid, commit record index} slot
+// pairs (one 16-byte access per probe), one slot per commit record, sized on
+// the device from the number of commit records (a power of two >= 1.5x, so a
+// log of 10M commits probes a 256 MiB table that the MALL can hold).  A slot
+// is free while its index word is EMPTY (a record index is below 2^31); the
+// txid word may hold any value, 2^64 - 1 included.
 __global__ void k_count_commits(agn_log_records r, unsigned long long *cnt) {
     uint64_t c = 0;
     for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < r.n;
@@ -69,23 +78,29 @@ __global__ void k_fill(uint64_t *tab, const unsigned long long *cnt) {
     }
 }
 
-__global__ void k_commit_map(agn_log_records r, uint64_t *tab, const unsigned long long *cnt) {
+// cnt[0] = commit records, cnt[1] = those that passed a slot of their own txid
+__global__ void k_commit_map(agn_log_records r, uint64_t *tab, unsigned long long *cnt) {
     const uint64_t mask = table_mask(cnt);
+    uint64_t dups = 0;
     for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < r.n;
          x += (uint64_t)gridDim.x * blockDim.x) {
         if (r.kind[x] != AGN_REC_COMMIT) continue;
         const uint64_t t = r.txid[x];
         uint64_t s = slot_of(t, mask);
         for (;;) {
-            const uint64_t prev = atomicCAS((unsigned long long *)&tab[2 * s],
-                                            (unsigned long long)EMPTY, (unsigned long long)t);
-            if (prev == EMPTY || prev == t) {
-                atomicMin((unsigned long long *)&tab[2 * s + 1], (unsigned long long)x);
+            const uint64_t prev = atomicCAS((unsigned long long *)&tab[2 * s + 1],
+                                            (unsigned long long)EMPTY, (unsigned long long)x);
+            if (prev == EMPTY) {
+                tab[2 * s] = t;
                 break;
             }
+            // the claimant's txid from its record: its slot's txid word may
+            // not be written yet
+            dups += r.txid[prev] == t;
             s = (s + 1) & mask;
         }
     }
+    if (dups) atomicAdd(cnt + 1, (unsigned long long)dups);
 }
 
 typedef unsigned long long u64x2i __attribute__((ext_vector_type(2)));
@@ -97,6 +112,7 @@ __global__ void k_join(agn_log_records r, uint32_t D, const uint64_t *__restrict
                        uint32_t *__restrict__ sval, unsigned long long *__restrict__ n_out) {
     const uint32_t W = n_words(D);
     const uint64_t mask = table_mask(cnt);
+    const bool unique = cnt[1] == 0;  // no txid has two commit records
     const u64x2i *slots = reinterpret_cast<const u64x2i *>(tab);
     uint64_t emitted = 0;
     for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < r.n;
@@ -107,10 +123,15 @@ __global__ void k_join(agn_log_records r, uint32_t D, const uint64_t *__restrict
             uint64_t s = slot_of(t, mask), c = EMPTY;
             for (;;) {
                 const u64x2i h = slots[s];
-                if (h.x == EMPTY) break;
+                if (h.y == EMPTY) break;
                 if (h.x == t) {
-                    c = h.y;
-                    break;
+                    if (unique) {
+                        c = h.y;
+                        break;
+                    }
+                    // the first commit record of the txid after this update:
+                    // every record of a txid lies in its cluster
+                    if (h.y > x && h.y < c) c = h.y;
                 }
                 s = (s + 1) & mask;
             }
@@ -247,7 +268,8 @@ int launch_log_ingest(const agn_log_records &r, uint32_t D, uint64_t n_keys,
     void *tmp = scratch;
     uint64_t *tab = (uint64_t *)(scratch + tb);
     uint64_t *k0 = tab + 2 * T, *k1 = k0 + n;
-    unsigned long long *n_out = (unsigned long long *)(k1 + n);  // [0] emitted, [2] commits
+    // [0] emitted, [2] commits, [3] commits of a txid that has an earlier one
+    unsigned long long *n_out = (unsigned long long *)(k1 + n);
     uint32_t *v0 = (uint32_t *)(n_out + 4), *v1 = v0 + (n + 1) / 2 * 2;
     uint32_t *rlen = v1 + (n + 1) / 2 * 2;
     const unsigned g = 2048;

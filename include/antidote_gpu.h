@@ -90,7 +90,10 @@ extern "C" {
 
 /* ---- value domain ------------------------------------------------------
  * What agn_log / agn_read fields may hold; every kernel is tested bit-exact
- * against the oracle over all of it (tests/test_value_domain.py):
+ * against the oracle over all of it (tests/test_value_domain.py; the log
+ * ingest, agn_gst_* and agn_dep_check on constructed edge cases in
+ * tests/test_small_kernels.py, their reach checked in
+ * tests/test_small_kernels_cpu.py):
  *   clock entries (oc, R, sct, snapshot-cache clocks, GC thresholds, the rows
  *     of agn_select_base / agn_dep_check / agn_gst_*): a PRESENT entry is any
  *     u64 <= 2^64 - 2, 0 included; they are compared unsigned.  UINT64_MAX is
@@ -103,7 +106,8 @@ extern "C" {
  *   tag / base_tag: any u32 but 0xFFFFFFFF (AGN_TAG_INVALID, reserved).
  *   op_id: any u32 but 0xFFFFFFFF (AGN_ID0_NONE, reserved by the id index);
  *     `hole` is the id zero-extended to int64, or id - 1.
- *   txid: any non-zero u64; 0 means "none" in the log and in a read. */
+ *   txid: any non-zero u64, 2^64 - 1 included; 0 means "none" in the log and
+ *     in a read. */
 
 /* ---- op log (device or host pointers, same layout) -------------------- */
 typedef struct agn_log {
@@ -523,7 +527,10 @@ int agn_select_base(agn_ctx *ctx, uint32_t n_dcs, uint64_t n_req,
  * UINT64_MAX; defined[n_epochs*P] = 0 marks an `undefined` partition
  * (NULL: all defined).  Output out[n_epochs][D+1]: per-DC min (UINT64_MAX =
  * DC absent from every partition), word D = 1 if every partition was defined
- * else 0.  agn_gst_finalize applies the "undefined => 0" rule (:78-84). */
+ * else 0.  An undefined partition's clocks are not read into the minimum.
+ * agn_gst_finalize applies the "undefined => 0" rule (:78-84).
+ * 1 <= n_dcs <= 4096; any other width returns AGN_ENOTSUP and launches
+ * nothing.  `clocks` needs 8-byte alignment only. */
 int agn_gst_min(agn_ctx *ctx, uint32_t n_dcs, uint64_t n_parts, uint64_t n_epochs,
                 const uint64_t *clocks, const uint8_t *defined, uint64_t *out,
                 void *stream);
@@ -687,7 +694,10 @@ typedef struct agn_log_records {
 
 /* logging_vnode get_ops_from_log / filter_terms_for_key / handle_commit
  * (src/logging_vnode.erl:522-549, 660-779) for every key at once: an update
- * is committed by the first later commit record of its transaction; it is
+ * is committed by the first later commit record of its transaction (a txid
+ * may have several commit records: handle_commit erases the transaction, so
+ * updates after one commit record wait for the next, and a commit record
+ * with no update since the previous one commits nothing); it is
  * emitted iff check_max_time(CommitSnapshotTime, MaxSnapshotTime) holds
  * (max_time[n_keys][D] + mask per key, NULL = undefined, i.e. recovery
  * get_all); per key the emitted ops keep commit order, then update order
@@ -701,7 +711,9 @@ typedef struct agn_log_records {
  * Keys index the partition's key space [0, n_keys): a partition's log holds
  * only its own keys (every update is logged at its key's partition,
  * src/log_utilities.erl:58-68), and a record naming a key outside it is
- * another partition's and is skipped.  Requires n_keys < 2^24 and n < 2^40. */
+ * another partition's and is skipped.  Requires n_keys < 2^24,
+ * recs->n < 2^31 - 1 and 1 <= n_dcs <= 256 (AGN_ENOTSUP / AGN_EINVAL
+ * otherwise). */
 int agn_log_ingest(agn_ctx *ctx, const agn_log_records *recs, uint32_t crdt_type,
                    uint32_t n_dcs, uint64_t n_keys, const uint64_t *max_time,
                    const uint64_t *max_time_mask, uint32_t op_id_base, agn_log *out,
@@ -757,7 +769,11 @@ int agn_gst_scalar(agn_ctx *ctx, uint32_t n_dcs, uint64_t n_epochs, uint64_t *ve
  * of its partition's clock in part_clock[n_parts][D] (+ part_mask).  Each
  * transaction is checked against the given clocks (the caller applies the
  * in-order queue semantics: the first blocked transaction stops its queue).
- * out_ok[n_txn] = 1 if applicable.  Device pointers. */
+ * out_ok[n_txn] = 1 if applicable.  An origin >= n_dcs names a DC outside
+ * the clocks: no column is exempt (set_clock_of_dc adds a 0 entry on both
+ * sides).  A transaction whose part[t] >= n_parts names no known partition
+ * clock: out_ok[t] = 0, the other transactions are unaffected.
+ * Device pointers. */
 int agn_dep_check(agn_ctx *ctx, uint32_t n_dcs, uint64_t n_txn, const uint64_t *deps,
                   const uint64_t *deps_mask, const uint32_t *origin, const uint32_t *part,
                   uint64_t n_parts, const uint64_t *part_clock, const uint64_t *part_mask,
