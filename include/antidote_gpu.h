@@ -93,7 +93,9 @@ extern "C" {
  * against the oracle over all of it (tests/test_value_domain.py; the log
  * ingest, agn_gst_* and agn_dep_check on constructed edge cases in
  * tests/test_small_kernels.py, their reach checked in
- * tests/test_small_kernels_cpu.py):
+ * tests/test_small_kernels_cpu.py; the snapshot cache, agn_read_cached, the
+ * cached batcher and agn_select_base at their slot and policy edges in
+ * tests/test_cache_edges.py, reach in tests/test_cache_edges_cpu.py):
  *   clock entries (oc, R, sct, snapshot-cache clocks, GC thresholds, the rows
  *     of agn_select_base / agn_dep_check / agn_gst_*): a PRESENT entry is any
  *     u64 <= 2^64 - 2, 0 included; they are compared unsigned.  UINT64_MAX is

@@ -185,8 +185,15 @@ def py_model(cs):
 def test_oracle_cache_vs_dict_restatement(oracle_lib, D, sparse):
     cs = Case(100 + D + sparse, 300, D, sparse)
     a, out = run_oracle(oracle_lib, cs)
+    check_oracle_vs_model(cs, a, out)
+    assert out["prune"].any() and (out["status"] == _abi.SS_LOG).any()
+    assert (out["status"] == _abi.SS_HIT).any() and (out["status"] == _abi.SS_NEW).any()
+
+
+def check_oracle_vs_model(cs, a, out):
+    """run_oracle's cache arrays and outputs against py_model, key by key."""
+    D, sparse = cs.D, cs.sparse
     caches, looked, pruned = py_model(cs)
-    W = cs.W
     for i, k in enumerate(cs.keys):
         st, sct, base, first = looked[i]
         assert out["status"][i] == {"hit": _abi.SS_HIT, "new": _abi.SS_NEW, "log": _abi.SS_LOG}[st]
@@ -208,9 +215,7 @@ def test_oracle_cache_vs_dict_restatement(oracle_lib, D, sparse):
             got = vc(out["thr"][k], out["thrm"][k] if sparse else None, D)
             want = pruned[k] if sparse else {d: pruned[k].get(d, 0) for d in range(D)}
             assert got == want
-    assert out["prune"].any() and (out["status"] == _abi.SS_LOG).any()
-    assert (out["status"] == _abi.SS_HIT).any() and (out["status"] == _abi.SS_NEW).any()
-    _ = W
+    return caches, looked, pruned
 
 
 @pytest.mark.gpu
