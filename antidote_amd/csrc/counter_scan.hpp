@@ -358,6 +358,94 @@ __device__ __forceinline__ void q8_fold(const Q8Chunk &c, const uint64_t *__rest
     sum += (mine && !badv) ? c.ev : 0;
 }
 
+// q8_load / q8_fold in three steps, for a caller that fetches a chunk's
+// effects only once it knows which ops are included (k_counter_quad2): an
+// excluded or snapshot-covered op's effect is never read (q8_fold uses c.ev
+// under `mine` only), and it is 8 of the 72 bytes an op costs.
+// q8_load_rows: the chunk's quad rows alone.
+struct Q8Rows {
+    u64x2 x[4];
+};
+
+template <bool NT>
+__device__ __forceinline__ Q8Rows q8_load_rows(const uint64_t *__restrict__ oc, uint64_t off,
+                                               uint64_t b, uint64_t n_entries) {
+    const int lane = lane_id();
+    const u64x2 *rows = reinterpret_cast<const u64x2 *>(oc);
+    const uint64_t lim = n_entries * 4u - 1u;
+    Q8Rows c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint64_t u = (off + b) * 4u + (uint64_t)(j * AGN_WAVE + lane);
+        u = u < lim ? u : lim;  // past the log's end: clamped, masked in q8_verdict
+        c.x[j] = ld<NT>(rows + u);
+    }
+    return c;
+}
+
+// q8_verdict: everything q8_fold derives from the rows -- first_excl, cnt and
+// the ctA / ctB maxima -- and the chunk's 64-bit mask of included ops.
+template <bool WARM>
+__device__ __forceinline__ uint64_t q8_verdict(const Q8Rows &c, const uint64_t *__restrict__ txid,
+                                               uint64_t txr, uint64_t off, uint64_t b, uint64_t n,
+                                               uint64_t n_entries, uint64_t rA, uint64_t rB,
+                                               uint64_t sA, uint64_t sB, uint64_t &ctA,
+                                               uint64_t &ctB, uint32_t &cnt, int64_t &first_excl,
+                                               bool noR = false) {
+    const int lane = lane_id();
+    const int q = lane >> 2;
+    const uint64_t valid = (n - b >= (uint64_t)AGN_WAVE) ? ~0ull : ((1ull << (n - b)) - 1ull);
+    uint64_t bad = 0, gt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bad |= nib_any16(ballot(c.x[j].x > rA || c.x[j].y > rB)) << (16 * j);
+        if (WARM) gt |= nib_any16(ballot(c.x[j].x > sA || c.x[j].y > sB)) << (16 * j);
+    }
+    uint64_t nip = WARM ? gt : ~0ull;  // belongs_to_snapshot_op: not covered by SCT
+    if (txid != nullptr) {
+        uint64_t e = off + b + (uint64_t)lane;
+        e = e < n_entries - 1u ? e : n_entries - 1u;
+        nip |= ballot(txid[e] == txr);
+    }
+    if (noR) bad = ~0ull;
+    const uint64_t incl = valid & nip & ~bad, excl = valid & nip & bad;
+    if (first_excl < 0 && excl) first_excl = (int64_t)b + (int64_t)__builtin_ctzll(excl);
+    cnt += (uint32_t)__builtin_popcountll(incl);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool in = ((incl >> (16 * j + q)) & 1ull) != 0ull;
+        ctA = (in && c.x[j].x > ctA) ? c.x[j].x : ctA;
+        ctB = (in && c.x[j].y > ctB) ? c.x[j].y : ctB;
+    }
+    return incl;
+}
+
+// q8_load_eff: lane l's effect when op b + l is included (an included op lies
+// inside the key, so its address needs no clamp).  Every other lane reads
+// `dummy`, one in-bounds address the wave has fetched already: an address
+// select, not a branch (a branch around the load is waited for on the spot).
+// A chunk without an included op fetches no effect line.
+__device__ __forceinline__ int64_t q8_load_eff(const int64_t *__restrict__ eff, uint64_t off,
+                                               uint64_t b, uint64_t incl,
+                                               const int64_t *__restrict__ dummy) {
+    const int lane = lane_id();
+    const bool mine = ((incl >> lane) & 1ull) != 0ull;
+    const int64_t *p = mine ? eff + (off + b + (uint64_t)lane) : dummy;
+    return *p;
+}
+
+// q8_fold_eff: first_err and sum from the included ops' effects.
+__device__ __forceinline__ void q8_fold_eff(uint64_t incl, int64_t ev, uint64_t b, int64_t &sum,
+                                            int64_t &first_err) {
+    const bool mine = ((incl >> lane_id()) & 1ull) != 0ull;
+    const bool badv = mine && ev == AGN_EFFECT_INVALID;
+    if (first_err < 0) {
+        const uint64_t be = ballot(badv);
+        if (be) first_err = (int64_t)b + (int64_t)__builtin_ctzll(be);
+    }
+    sum += (mine && !badv) ? ev : 0;
+}
+
 // scan_key for D = 8 with lane-CONTIGUOUS row loads ("quad rows"): load j of a
 // 64-op chunk reads bytes [1 KiB j, 1 KiB (j+1)) of the chunk's rows, so
 // every instruction covers 8 whole 128-byte lines -- the row-per-lane loads

@@ -758,6 +758,158 @@ __device__ __forceinline__ void q2_epilogue(const Q2Key &k, Q2Acc &s, uint32_t h
     }
 }
 
+// q2_epilogue in steps, for k_counter_quad2's forms that run the two keys'
+// steps side by side (Q2_EFF, Q2_STORE below): the verdict of chunk 0 (q2_fold
+// without the effects), the LastOpCt fold, the request's result as values,
+// and the stores -- per key as q2_epilogue's, or one set for the pair.
+template <bool ANY_WARM>
+__device__ __forceinline__ uint64_t q2_verdict(const Q2Key &k, const Q8Rows &c,
+                                               const uint64_t *__restrict__ log_txid,
+                                               uint64_t n_entries, Q2Acc &s) {
+    const uint64_t *tx = k.txr ? log_txid : nullptr;
+    if (ANY_WARM && !k.sct_ign)
+        return q8_verdict<true>(c, tx, k.txr, k.off, 0, k.n, n_entries, k.rA, k.rB, k.sA, k.sB,
+                                s.ctA, s.ctB, s.cnt, s.first_excl, k.noR);
+    return q8_verdict<false>(c, tx, k.txr, k.off, 0, k.n, n_entries, k.rA, k.rB, k.sA, k.sB, s.ctA,
+                             s.ctB, s.cnt, s.first_excl, k.noR);
+}
+
+// LastOpCt: the 16 lanes of each part fold by xor-shuffles (no effect needed)
+template <bool MSK>
+__device__ __forceinline__ void q2_ctfold(const Q2Key &k, Q2Acc &s) {
+    if constexpr (MSK) {
+        if (k.uni) {  // outside U: SCT's value (an op's row there is not in its dict)
+            const int p = lane_id() & 3;
+            s.ctA = ((k.U >> (2 * p)) & 1ull) ? s.ctA : k.eA;
+            s.ctB = ((k.U >> (2 * p + 1)) & 1ull) ? s.ctB : k.eB;
+        }
+    }
+#pragma unroll
+    for (int x = 4; x < AGN_WAVE; x <<= 1) {
+        s.ctA = umax64(s.ctA, shfl_xor_u64(s.ctA, x));
+        s.ctB = umax64(s.ctB, shfl_xor_u64(s.ctB, x));
+    }
+}
+
+struct Q2Out {
+    int64_t value, hole;
+    uint32_t cnt, fl, err;
+    uint64_t mo;
+    bool ct_ign;
+    bool wm;  // MSK: the request writes its lastct_mask word
+};
+
+// A served (not corrupt) request's result, after the scan and q2_ctfold.
+template <bool MSK>
+__device__ __forceinline__ Q2Out q2_result(const Q2Key &k, const Q2Acc &s, uint32_t hints,
+                                           const uint32_t *__restrict__ op_id,
+                                           const int64_t *__restrict__ base_value, bool has_mask) {
+    constexpr int D = 8;
+    int64_t hid;
+    const uint64_t pos = s.first_excl >= 0 ? (uint64_t)s.first_excl : k.n - 1;
+    if (k.id0 != AGN_ID0_NONE)
+        hid = k.n ? (int64_t)((uint64_t)k.id0 + pos) : 0;
+    else
+        hid = k.n ? (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
+                        (int)ldc(op_id + uniform_u64(k.off + pos))) : 0;
+    const int64_t base = base_value ? (int64_t)uniform_u64((uint64_t)ldc(base_value + k.i)) : 0;
+    const int64_t total = wave_sum_dpp(s.sum);
+    Q2Out r;
+    r.ct_ign = k.sct_ign && s.cnt == 0u;
+    r.mo = 0;
+    if constexpr (MSK) {
+        const uint64_t un = k.uni ? (s.cnt ? k.U : 0ull) : wave_or_bits<D>(s.um);
+        r.mo = r.ct_ign ? 0ull : ((k.sct_ign ? 0ull : k.Sm) | un);
+    }
+    r.value = (int64_t)((uint64_t)base + (uint64_t)total);
+    r.hole = s.first_excl >= 0 ? hid - 1 : hid;
+    r.cnt = s.cnt;
+    r.fl = 0;
+    if (s.cnt) r.fl |= AGN_F_NEWSS;
+    if (r.ct_ign) r.fl |= AGN_F_CT_IGNORE;
+    if (s.first_err >= 0) r.fl |= AGN_F_ERR_UNEXPECTED;
+    r.err = s.first_err >= 0 ? (uint32_t)(k.off + (uint64_t)s.first_err) : 0xffffffffu;
+    const bool full = MSK && (hints & AGN_HINT_CT_FLAG) && r.mo == 0xFFull;  // q2_epilogue
+    if (full) r.fl |= AGN_F_CT_FULL;
+    r.wm = MSK && has_mask && !full;
+    return r;
+}
+
+// One request's stores (q2_epilogue's).
+__device__ __forceinline__ void q2_store(const Q2Key &k, const Q2Acc &s, const Q2Out &r,
+                                         int64_t *__restrict__ o_value,
+                                         int64_t *__restrict__ o_hole,
+                                         uint64_t *__restrict__ o_lastct,
+                                         uint32_t *__restrict__ o_count,
+                                         uint32_t *__restrict__ o_flags,
+                                         uint32_t *__restrict__ o_err,
+                                         uint64_t *__restrict__ o_mask) {
+    const int lane = lane_id();
+    const uint64_t i = k.i;
+    if (k.corrupt) {
+        if (lane == 0) {  // erlang:error(corrupted_ops_cache) (:190-191)
+            o_flags[i] = AGN_F_ERR_CORRUPTED;
+            o_err[i] = 0xffffffffu;
+        }
+        return;
+    }
+    if (lane < 4) {
+        u64x2 v;
+        v.x = r.ct_ign ? 0ull : s.ctA;
+        v.y = r.ct_ign ? 0ull : s.ctB;
+        reinterpret_cast<u64x2 *>(o_lastct + i * 8u)[lane] = v;
+    }
+    if (lane == 0) {
+        o_value[i] = r.value;
+        o_hole[i] = r.hole;
+        o_count[i] = r.cnt;
+        o_err[i] = r.err;
+        o_flags[i] = r.fl;
+        if (r.wm) o_mask[i] = r.mo;
+    }
+}
+
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// Requests i0 (even) and i0 + 1, both served: their slots are adjacent in
+// every result array, so each array takes one store -- the two LastOpCt rows
+// are one 128-byte line, written by lanes 0-3 (key 0) and 4-7 (key 1).  Six
+// store instructions per wave where two q2_store issue twelve; the arrays'
+// alignment is the launcher's condition (launch_quad2).
+__device__ __forceinline__ void q2_store2(uint64_t i0, const Q2Acc &s0, const Q2Acc &s1,
+                                          const Q2Out &r0, const Q2Out &r1,
+                                          int64_t *__restrict__ o_value,
+                                          int64_t *__restrict__ o_hole,
+                                          uint64_t *__restrict__ o_lastct,
+                                          uint32_t *__restrict__ o_count,
+                                          uint32_t *__restrict__ o_flags,
+                                          uint32_t *__restrict__ o_err,
+                                          uint64_t *__restrict__ o_mask) {
+    const int lane = lane_id();
+    if (lane < 8) {
+        const bool hi = lane >= 4;
+        const bool ign = hi ? r1.ct_ign : r0.ct_ign;
+        u64x2 v;
+        v.x = ign ? 0ull : (hi ? s1.ctA : s0.ctA);
+        v.y = ign ? 0ull : (hi ? s1.ctB : s0.ctB);
+        reinterpret_cast<u64x2 *>(o_lastct + i0 * 8u)[lane] = v;
+    }
+    if (lane == 0) {
+        *reinterpret_cast<i64x2 *>(o_value + i0) = i64x2{r0.value, r1.value};
+        *reinterpret_cast<i64x2 *>(o_hole + i0) = i64x2{r0.hole, r1.hole};
+        *reinterpret_cast<u32x2 *>(o_count + i0) = u32x2{r0.cnt, r1.cnt};
+        *reinterpret_cast<u32x2 *>(o_err + i0) = u32x2{r0.err, r1.err};
+        *reinterpret_cast<u32x2 *>(o_flags + i0) = u32x2{r0.fl, r1.fl};
+        if (r0.wm && r1.wm) {
+            *reinterpret_cast<u64x2 *>(o_mask + i0) = u64x2{r0.mo, r1.mo};
+        } else {
+            if (r0.wm) o_mask[i0] = r0.mo;
+            if (r1.wm) o_mask[i0 + 1u] = r1.mo;
+        }
+    }
+}
+
 // k_counter_q8e2's parameters as one block (kparams: each stage reads the
 // fields it uses; as 26 separate arguments it spilled 62 SGPRs, 43-47 so).
 // k_counter_quad2 keeps its by-value arguments: read this way its dense warm
@@ -794,7 +946,21 @@ __device__ __forceinline__ MaskArgs mask_of(const T &x) {
 // spills instead of 84 VGPRs (5 waves) and 24 spilled SGPRs, 8.13 against
 // 8.33 ms on warm cfg2 (profiles/r05/ab_quad2_w6.log).  The masked forms spill
 // far more under that budget and keep the default.
-template <bool ANY_WARM, bool MSK>
+//
+// Q2_EFF (AGN_Q2_EFF): chunk 0's effects are fetched after the verdict, by the
+// included ops' lanes only.  The wave issues both keys' rows, then per key
+// computes the verdict (q2_verdict) and issues the effect load (q8_load_eff;
+// the other lanes read the request's R row, which q2_load has fetched), runs
+// both keys' LastOpCt folds under those loads, folds the effects, and only
+// then stores: loads and stores share one VM counter, and a store between an
+// effect load and its use would make that wait vmcnt(0).
+// Q2_STORE (AGN_Q2_STORE): one set of stores for a pair of served requests
+// (q2_store2); a pair with a corrupt request and an unpaired last request
+// store per key.
+// Both forms serve the pairs whose two keys fit one chunk; a pair with a
+// longer key (or, masked, a mixed one) runs the kernel as it was before
+// either, and so does every pair when both are 0.
+template <bool ANY_WARM, bool MSK, bool Q2_EFF, bool Q2_STORE>
 __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad2(
     DenseArgs a, MaskArgs mk, const uint64_t *__restrict__ keys,
     const uint64_t *__restrict__ key_off, const uint64_t *__restrict__ key_len,
@@ -821,6 +987,71 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
     s0.ctB = k0.eB;
     s1.ctA = k1.eA;
     s1.ctB = k1.eB;
+    if constexpr (Q2_EFF || Q2_STORE) {
+        // The straight path: both keys within one chunk and on the dense
+        // scan, so no loop lies between the loads and the stores (behind a
+        // loop's exit the effects were waited for before the folds).  Any
+        // other pair runs the code below, as before.
+        const bool one = k0.n <= (uint64_t)AGN_WAVE && k1.n <= (uint64_t)AGN_WAVE;
+        if (a.n_entries != 0 && one && (!MSK || (k0.uni && k1.uni))) {
+            const bool d0 = !k0.corrupt, d1 = !k1.corrupt;
+            uint64_t in0 = 0, in1 = 0;  // chunk 0's included ops
+            int64_t ev0 = 0, ev1 = 0;   // and their effects (lane = op)
+            if constexpr (Q2_EFF) {
+                const Q8Rows c0 = q8_load_rows<true>(oc, k0.off, 0, a.n_entries);
+                const Q8Rows c1 = q8_load_rows<true>(oc, k1.off, 0, a.n_entries);
+                __builtin_amdgcn_sched_barrier(0);
+                // the verdicts run unconditionally and are dropped for a corrupt
+                // key: under a branch on d0 the compiler sinks k0's row loads
+                // into it, behind k1's
+                Q2Acc t0 = s0, t1 = s1;
+                in0 = q2_verdict<ANY_WARM>(k0, c0, log_txid, a.n_entries, t0);
+                in0 = d0 ? in0 : 0ull;
+                if (d0) s0 = t0;
+                ev0 = q8_load_eff(eff, k0.off, 0, in0, reinterpret_cast<const int64_t *>(R + k0.i * 8u));
+                in1 = q2_verdict<ANY_WARM>(k1, c1, log_txid, a.n_entries, t1);
+                in1 = d1 ? in1 : 0ull;
+                if (d1) s1 = t1;
+                ev1 = q8_load_eff(eff, k1.off, 0, in1, reinterpret_cast<const int64_t *>(R + k1.i * 8u));
+                __builtin_amdgcn_sched_barrier(0);  // both effect loads are in flight from here
+            } else {
+                const Q8Chunk c0 = q8_load<true, false>(oc, eff, k0.off, 0, a.n_entries);
+                const Q8Chunk c1 = q8_load<true, false>(oc, eff, k1.off, 0, a.n_entries);
+                __builtin_amdgcn_sched_barrier(0);
+                if (d0) q2_fold<ANY_WARM>(k0, c0, 0, log_txid, a.n_entries, s0);
+                if (d1) q2_fold<ANY_WARM>(k1, c1, 0, log_txid, a.n_entries, s1);
+            }
+            // The pointers the results need are read from the kernarg segment
+            // here, under the effect loads, instead of as arguments: held in
+            // SGPRs from the kernel's entry they crowd the scan's scalar state
+            // out to VGPR lanes.  Q2Params lists this kernel's parameters in
+            // order.
+            const auto &pr = kparams<Q2Params>();
+            const uint32_t *const l_op_id = pr.op_id;
+            const int64_t *const l_base = pr.base_value;
+            int64_t *const l_value = pr.o_value, *const l_hole = pr.o_hole;
+            uint64_t *const l_lastct = pr.o_lastct;
+            uint32_t *const l_count = pr.o_count, *const l_flags = pr.o_flags, *const l_err = pr.o_err;
+            q2_ctfold<MSK>(k0, s0);
+            q2_ctfold<MSK>(k1, s1);
+            if constexpr (Q2_EFF) {
+                __builtin_amdgcn_sched_barrier(0);  // the wait for the effects: after the folds
+                q8_fold_eff(in0, ev0, 0, s0.sum, s0.first_err);
+                q8_fold_eff(in1, ev1, 0, s1.sum, s1.first_err);
+                __builtin_amdgcn_sched_barrier(0);  // and no store before it
+            }
+            Q2Out r0{}, r1{};
+            if (d0) r0 = q2_result<MSK>(k0, s0, a.hints, l_op_id, l_base, mk.o_mask != nullptr);
+            if (two && d1) r1 = q2_result<MSK>(k1, s1, a.hints, l_op_id, l_base, mk.o_mask != nullptr);
+            if (Q2_STORE && two && d0 && d1) {
+                q2_store2(i0, s0, s1, r0, r1, l_value, l_hole, l_lastct, l_count, l_flags, l_err, mk.o_mask);
+            } else {
+                q2_store(k0, s0, r0, l_value, l_hole, l_lastct, l_count, l_flags, l_err, mk.o_mask);
+                if (two) q2_store(k1, s1, r1, l_value, l_hole, l_lastct, l_count, l_flags, l_err, mk.o_mask);
+            }
+            return;
+        }
+    }
     if (a.n_entries != 0) {
         const Q8Chunk c0 = q8_load<true, false>(oc, eff, k0.off, 0, a.n_entries);
         const Q8Chunk c1 = q8_load<true, false>(oc, eff, k1.off, 0, a.n_entries);
@@ -836,6 +1067,15 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
             if (!k1.corrupt && !k1.uni)
                 q2_msk<ANY_WARM>(k1, oc, mk.oc_mask, eff, log_txid, a.n_entries, s1);
         }
+    }
+    if constexpr (Q2_EFF || Q2_STORE) {  // no result pointer held as an argument (see above)
+        const auto &pe = kparams<Q2Params>();
+        q2_epilogue<MSK>(k0, s0, a.hints, pe.op_id, pe.base_value, pe.o_value, pe.o_hole, pe.o_lastct,
+                         pe.o_count, pe.o_flags, pe.o_err, mk.o_mask);
+        if (two)
+            q2_epilogue<MSK>(k1, s1, a.hints, pe.op_id, pe.base_value, pe.o_value, pe.o_hole,
+                             pe.o_lastct, pe.o_count, pe.o_flags, pe.o_err, mk.o_mask);
+        return;
     }
     q2_epilogue<MSK>(k0, s0, a.hints, op_id, base_value, o_value, o_hole, o_lastct, o_count, o_flags, o_err,
                      mk.o_mask);
@@ -1051,13 +1291,38 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
     const uint64_t nb = (req.n_req + 1) / 2;
     if (nb > 0x7fffffffull) return fail(AGN_EINVAL, "batch too large: %llu requests",
                                         (unsigned long long)req.n_req);
+#define AGN_Q2L_(W, M, E, S)                                                                    \
+    hipLaunchKernelGGL((k_counter_quad2<W, M, E, S>), dim3((unsigned)nb), dim3(64), 0, st, a,   \
+                       mk, req.keys, log.key_off, log.key_len, log.key_type, id0_index(log),    \
+                       log.oc, log.op_id, log.eff, log.txid, req.R, req.sct, req.sct_ignore,    \
+                       req.txid, req.base_value, out.value, out.hole, out.lastct, out.count,    \
+                       out.flags, out.err_pos)
 #define AGN_Q2L(W, M)                                                                           \
-    hipLaunchKernelGGL((k_counter_quad2<W, M>), dim3((unsigned)nb), dim3(64), 0, st, a, mk,     \
-                       req.keys, log.key_off, log.key_len, log.key_type, id0_index(log), log.oc, \
-                       log.op_id, log.eff, log.txid, req.R, req.sct, req.sct_ignore, req.txid,  \
-                       req.base_value, out.value, out.hole, out.lastct, out.count, out.flags,   \
-                       out.err_pos)
+    do {                                                                                        \
+        if (q2e && q2s) AGN_Q2L_(W, M, true, true);                                             \
+        else if (q2e) AGN_Q2L_(W, M, true, false);                                              \
+        else if (q2s) AGN_Q2L_(W, M, false, true);                                              \
+        else AGN_Q2L_(W, M, false, false);                                                      \
+    } while (0)
     const bool msk = sparse_batch(log, req, out);
+    // AGN_Q2_EFF / AGN_Q2_STORE = 0|1 (A/B knobs; k_counter_quad2).  Both are
+    // the default of the cold dense path: cold cfg2 in one process 7.72 ms
+    // before, 7.54 with the effects after the verdict, 7.66 with the paired
+    // stores, 7.39 with both (62 VGPRs, 98 SGPRs, 8 waves per SIMD, no spill).
+    // The warm dense path keeps the kernel as it was (8.13 ms against 8.52 /
+    // 8.93 / 8.31: under its 6-wave budget the forms spill 44-48 bytes per
+    // lane), and so do the masked forms, which lose a wave per SIMD or gain
+    // SGPR spills (profiles/r07/ab_q2_eff_store_*.log, resource_usage_quad2.txt).
+    // The pair stores write 16 bytes to the 8-byte arrays and 8 to the 4-byte
+    // ones: result arrays that are not aligned so keep the per-key stores.
+    const bool dflt = !req.sct && !msk;
+    const char *ev = AGN_KNOB("AGN_Q2_EFF"), *sv = AGN_KNOB("AGN_Q2_STORE");
+    const bool q2e = (ev && (ev[0] == '0' || ev[0] == '1')) ? ev[0] == '1' : dflt;
+    const uintptr_t a16 = (uintptr_t)out.value | (uintptr_t)out.hole | (uintptr_t)out.lastct |
+                          (uintptr_t)mk.o_mask;
+    const uintptr_t a8 = (uintptr_t)out.count | (uintptr_t)out.flags | (uintptr_t)out.err_pos;
+    const bool q2s = ((sv && (sv[0] == '0' || sv[0] == '1')) ? sv[0] == '1' : dflt) &&
+                     (a16 & 15u) == 0 && (a8 & 7u) == 0;
     if (req.sct) {
         if (msk) AGN_Q2L(true, true);
         else AGN_Q2L(true, false);
@@ -1066,6 +1331,7 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
         else AGN_Q2L(false, false);
     }
 #undef AGN_Q2L
+#undef AGN_Q2L_
     AGN_HIP(hipGetLastError());
     return AGN_OK;
 }

@@ -23,6 +23,7 @@ ap.add_argument("--var", action="append", default=[])
 ap.add_argument("--rounds", type=int, default=12)
 ap.add_argument("--keys", type=int, default=0)
 ap.add_argument("--warm", type=int, default=0)
+ap.add_argument("--ops", type=int, default=0, help="override ops per key")
 a = ap.parse_args()
 VARS = {}
 for v in a.var:
@@ -33,7 +34,9 @@ FIELDS = ("value", "hole", "lastct", "count", "flags", "err_pos")
 eng = Engine(0)
 sp = torch.cuda.current_stream().cuda_stream
 for c in a.cfg or [2]:
-    cfg = CONFIGS[c]
+    cfg = dict(CONFIGS[c])
+    if a.ops:
+        cfg["ops_per_key"] = a.ops
     K = a.keys or cfg["n_keys"]
     g = _abi.AgnGenCfg(crdt_type=cfg["crdt_type"], n_dcs=cfg["n_dcs"], n_keys=K,
                        ops_per_key=cfg["ops_per_key"], n_elems=cfg["n_elems"], seed=cfg["seed"],

@@ -26,9 +26,8 @@ LIBS = {}
 ENV_VARS = {}
 for a in (sys.argv[2:] or ["prev=tools/libagn_prev.so"]):
     name, path = a.split("=", 1)
-    if path.startswith("env:"):  # name=env:KEY=VAL: the current library with an env knob
-        k, v = path[4:].split("=", 1)
-        ENV_VARS[name] = {k: v}
+    if path.startswith("env:"):  # name=env:KEY=VAL[,KEY=VAL]: the current library with env knobs
+        ENV_VARS[name] = dict(x.split("=", 1) for x in path[4:].split(","))
         continue
     lib = C.CDLL(os.path.join(ROOT, path), mode=os.RTLD_LOCAL)
     _abi.bind(lib, {k: v for k, v in _abi.PROTOTYPES.items() if hasattr(lib, k)})

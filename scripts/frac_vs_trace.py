@@ -14,13 +14,13 @@ import sys
 
 # bench line -> a substring of its dominant kernel's demangled name
 KERNELS = {
-    "cfg2": "k_counter_quad2<false, false>",
+    "cfg2": "k_counter_quad2<false, false,",
     "cfg1": "k_counter_key<3,",
     "cfg2_masked_full": "k_counter_q8e2<false",
     "cfg3": "k_tags<4, 4, false, true, true, 256, 1, 2, false, false, true, false",
     "cfg4": "k_tags<4, 16, false, true, false, 256, 1, 2, false, false",
     "cfg5": "k_gst_cols",
-    "cfg2_warm": "k_counter_quad2<true, false>",
+    "cfg2_warm": "k_counter_quad2<true, false,",
     "cfg3_warm": "k_tags<4, 4, false, true, true, 256, 1, 2, true, false",
     "cfg4_warm": "k_tags<4, 16, false, true, false, 256, 1, 2, true, false",
     "cfg3_gc": "k_prune_inplace<8, 2, false, true, true",
