@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 OK = 0
 EINVAL, EHIP, ENOMEM, ECAPACITY, ENOTSUP, ERCCL, ENODEV = -1, -2, -3, -4, -5, -6, -7
@@ -185,6 +185,7 @@ PROTOTYPES = {
     "agn_oplog_key_meta": (C.c_int, [P, C.c_uint64, P, P, P, P]),
     "agn_oplog_gc_due": (C.c_int, [P, C.c_uint64, P, P]),
     "agn_oplog_set_counter": (C.c_int, [P, C.c_uint64, P, P]),
+    "agn_oplog_load": (C.c_int, [P, C.POINTER(AgnLog), P]),
     "agn_interner_create": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(P)]),
     "agn_interner_destroy": (C.c_int, [P]),
     "agn_intern": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),

@@ -39,9 +39,17 @@
 // next prune first re-lays the arenas out (relayout: fresh arenas sized
 // max(ListLen, length) per key, one copy kernel), allocating everything
 // before it changes any state.
+//
+// Recovery.  agn_oplog_load fills a pristine log from a device log (the
+// ingested CSR, or another log's view) without the host path: the kernels of
+// oplog_load.hip index the source per key, scan the segment starts and copy
+// every key's runs into arenas of exactly the laid-out size; the host reads
+// the per-key records back while the copy runs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -988,6 +996,235 @@ int agn_oplog_set_counter(agn_oplog *L, uint64_t n, const uint64_t *keys, const 
             return fail(AGN_EINVAL, "oplog_set_counter: key %llu >= n_keys", (unsigned long long)keys[i]);
     for (uint64_t i = 0; i < n; ++i) L->counter[keys[i]] = counter[i];
     return AGN_OK;
+}
+
+// Recovery: a device log into the pristine log, device to device.  Index pass
+// (per-key records, the slots each key takes) and their scan into segment
+// starts -> host: the totals alone decide the refusals and size the arenas,
+// which are allocated before any state changes -> key arrays -> the copy
+// pass.  The records travel to the host on a stream of their own while the
+// copy pass runs, and the host fills its per-key metadata from them under it.
+static int oplog_load_locked(agn_oplog *L, const agn_log &src, hipStream_t st) {
+    const uint64_t K = L->K, K1 = std::max<uint64_t>(K, 1);
+    if (L->n_entries || L->used || L->tused || !L->s_key.empty() || !L->dirty_keys.empty() ||
+        !L->moves.empty())
+        return fail(AGN_EINVAL, "oplog_load: the log holds entries or segments");
+    for (uint64_t k = 0; k < K; ++k)
+        if (L->counter[k])
+            return fail(AGN_EINVAL, "oplog_load: key %llu has op counter %u",
+                        (unsigned long long)k, L->counter[k]);
+    if (K == 0) return AGN_OK;
+    if (K > 0x7fffffffull) return fail(AGN_ENOTSUP, "oplog_load: %llu keys", (unsigned long long)K);
+    // AGN_LOAD_TRACE=1: the call's phases on stderr (ms)
+    using clk = std::chrono::steady_clock;
+    clk::time_point tp[6];
+    const auto mark = [&](int i) { tp[i] = clk::now(); };
+    mark(0);
+    // device scratch: last id [K] | DC set [K] | starts [K + 1] | token starts
+    // [K + 1] | bad | scan scratch; the u32 records go to d_meta's rows
+    const bool um = !L->umask.empty();
+    const size_t scan_bytes = load_scan_bytes(K);
+    if (!scan_bytes) return fail(AGN_EHIP, "oplog_load: scan sizing");
+    size_t off = 0;
+    auto slot = [&](size_t bytes) { size_t o = off; off = align8(off + bytes); return o; };
+    const size_t o_last = slot(K * 4), o_um = slot(um ? K * 8 : 0), o_s = slot((K + 1) * 8),
+                 o_ts = slot(L->tags ? (K + 1) * 8 : 0), o_bad = slot(4), o_scan = slot(scan_bytes);
+    char *d_tmp = nullptr;
+    AGN_HIP(pool_malloc((void **)&d_tmp, off, st));
+    uint64_t *const d_start = (uint64_t *)(d_tmp + o_s);
+    uint64_t *const d_tstart = L->tags ? (uint64_t *)(d_tmp + o_ts) : nullptr;
+    LoadIndex ix;
+    ix.len = L->d_meta;
+    ix.tlen = L->d_meta + K1;
+    ix.lcap = L->d_meta + 2 * K1;
+    ix.id0 = L->d_meta + 3 * K1;
+    ix.last = (uint32_t *)(d_tmp + o_last);
+    ix.umask = um ? (uint64_t *)(d_tmp + o_um) : nullptr;
+    ix.slots = d_start + 1;
+    ix.tslots = d_tstart ? d_tstart + 1 : nullptr;
+    ix.bad = (uint32_t *)(d_tmp + o_bad);
+    uint32_t bad = 0;
+    uint64_t used = 0, tused = 0;
+    hipError_t e = hipMemsetAsync(ix.bad, 0, 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_start, 0, 8, st);
+    if (e == hipSuccess && d_tstart) e = hipMemsetAsync(d_tstart, 0, 8, st);
+    int rc = e == hipSuccess ? launch_load_index(src, L->init_slots, ix, d_tmp + o_scan, scan_bytes, st)
+                             : AGN_OK;
+    if (e == hipSuccess && rc == AGN_OK)
+        e = hipMemcpyAsync(&bad, ix.bad, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == AGN_OK)
+        e = hipMemcpyAsync(&used, d_start + K, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == AGN_OK && d_tstart)
+        e = hipMemcpyAsync(&tused, d_tstart + K, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && rc == AGN_OK) e = hipStreamSynchronize(st);
+    mark(1);
+    // nothing of the log has changed so far
+    auto refuse = [&](int code, const char *what) {
+        (void)hipFreeAsync(d_tmp, st);
+        return fail(code, "oplog_load: %s", what);
+    };
+    if (e != hipSuccess) return refuse(AGN_EHIP, hipGetErrorString(e));
+    if (rc != AGN_OK) {
+        (void)hipFreeAsync(d_tmp, st);
+        return rc;
+    }
+    if (bad & 1u) return refuse(AGN_EINVAL, "an op id is 0, AGN_ID0_NONE or below its predecessor");
+    if (bad & 4u) return refuse(AGN_EINVAL, "removal tokens without rem_tok");
+    if (bad & 2u) return refuse(AGN_ENOTSUP, "a key's length or ListLen is beyond 32 bits");
+    if (used >= 0xffffffffull || tused >= 0xffffffffull)
+        return refuse(AGN_ENOTSUP, "arena beyond 2^32 slots");
+    // arenas of exactly the laid-out size, and the records' stream
+    const uint64_t U = std::max<uint64_t>(used, 1), TU = std::max<uint64_t>(tused, 1);
+    // (A/B knob AGN_LOAD_SIDE=0: the records on the caller's stream, ahead of
+    // the copy pass)
+    const char *knob = AGN_KNOB("AGN_LOAD_SIDE");
+    const bool own_side = !(knob && knob[0] == '0');
+    hipStream_t side = st;
+    Arena b;
+    e = own_side ? hipStreamCreateWithFlags(&side, hipStreamNonBlocking) : hipSuccess;
+    if (e != hipSuccess) side = nullptr;
+    if (e == hipSuccess) e = pool_malloc(&b.oc, U * L->D * 8, st);
+    if (e == hipSuccess && L->sparse) e = pool_malloc(&b.mask, U * L->W * 8, st);
+    if (e == hipSuccess) e = pool_malloc(&b.op_id, U * 4, st);
+    if (e == hipSuccess) e = pool_malloc(&b.txid, U * 8, st);
+    if (e == hipSuccess && !L->tags) e = pool_malloc(&b.eff, U * 8, st);
+    if (e == hipSuccess && L->tags) e = pool_malloc(&b.tag, U * 4, st);
+    if (e == hipSuccess && L->tags) e = pool_malloc(&b.add, U * 8, st);
+    if (e == hipSuccess && L->tags) e = pool_malloc(&b.rem_off, U * 4, st);
+    if (e == hipSuccess && L->tags) e = pool_malloc(&b.tok, TU * 8, st);
+    if (e != hipSuccess) {
+        for (void *p : {(void *)b.oc, (void *)b.mask, (void *)b.op_id, (void *)b.txid,
+                        (void *)b.eff, (void *)b.tag, (void *)b.add, (void *)b.rem_off,
+                        (void *)b.tok})
+            if (p) (void)hipFreeAsync(p, st);
+        if (own_side && side) (void)hipStreamDestroy(side);
+        return refuse(AGN_ENOMEM, hipGetErrorString(e));
+    }
+    mark(2);
+    // commit.  Device: key arrays and the records' live starts, then the copy
+    // pass, and beside it the records to the host (pinned rows; the last ids
+    // and DC sets straight into their vectors).
+    Arena &a = L->a;  // a flush of the empty log may have left one-slot arrays
+    for (void *p : {(void *)a.oc, (void *)a.mask, (void *)a.txid, (void *)a.add, (void *)a.op_id,
+                    (void *)a.tag, (void *)a.rem_off, (void *)a.eff, (void *)a.tok})
+        if (p) (void)hipFreeAsync(p, st);
+    L->a = b;
+    L->dcap = U;
+    L->tdcap = L->tags ? TU : 0;
+    L->used = L->live = used;
+    L->tused = L->tlive = tused;
+    L->relayout_wanted = false;
+    agn_log dst;
+    fill_view(L, &dst);
+    rc = launch_load_keys(K, ix.len, ix.id0, ix.lcap, d_start, d_tstart, ix.umask,
+                          L->d_meta + 4 * K1, L->d_meta + 5 * K1, L->key_off, L->key_len,
+                          L->key_id0, L->key_lcap, L->key_mask, st);
+    if (rc == AGN_OK && own_side) e = hipEventRecord(L->up_done, st);
+    if (rc == AGN_OK && own_side && e == hipSuccess) e = hipStreamWaitEvent(side, L->up_done, 0);
+    const auto records = [&]() {
+        if (rc == AGN_OK && e == hipSuccess)
+            e = hipMemcpyAsync(L->meta, L->d_meta, 6 * K1 * 4, hipMemcpyDeviceToHost, side);
+        if (rc == AGN_OK && e == hipSuccess)
+            e = hipMemcpyAsync(L->counter.data(), ix.last, K * 4, hipMemcpyDeviceToHost, side);
+        if (rc == AGN_OK && e == hipSuccess && um)
+            e = hipMemcpyAsync(L->umask.data(), ix.umask, K * 8, hipMemcpyDeviceToHost, side);
+        if (rc == AGN_OK && e == hipSuccess && !own_side) e = hipEventRecord(L->up_done, st);
+    };
+    if (!own_side) records();
+    // the entry count only picks the copy pass's lanes per key: src's when it
+    // is CSR, else (a view's n_entries counts slots) the slots laid out here
+    if (rc == AGN_OK && e == hipSuccess)
+        rc = launch_load_copy(src, dst, src.key_len ? std::min(src.n_entries, used) : src.n_entries,
+                              ix.len, ix.tlen, d_start, d_tstart, st);
+    if (own_side) records();
+    // the records are on the host (and the scratch may be freed) ...
+    const hipError_t e2 = own_side ? hipStreamSynchronize(side) : hipEventSynchronize(L->up_done);
+    (void)hipFreeAsync(d_tmp, st);
+    if (e == hipSuccess) e = e2;
+    // ... and the stream goes once the device is idle again: its queue is not
+    // torn down under the running copy pass
+    struct SideGuard {
+        hipStream_t s, st;
+        ~SideGuard() {
+            if (!s) return;
+            (void)hipStreamSynchronize(st);
+            (void)hipStreamDestroy(s);
+        }
+    } guard{own_side ? side : nullptr, st};
+    if (e != hipSuccess) return fail(AGN_EHIP, "oplog_load: %s", hipGetErrorString(e));
+    if (rc != AGN_OK) return rc;
+    mark(3);
+    // Host metadata from the records, while the copy pass runs.  The pristine
+    // log's cap / tcap are all 0.
+    uint64_t ne = 0, nt = 0;
+    for (uint64_t k = 0; k < K; ++k) {
+        L->start[k] = L->lstart[k];
+        const uint32_t l = L->len[k];
+        if (l == 0) continue;
+        L->cap[k] = L->lcap[k];
+        ne += l;
+    }
+    if (L->tags)
+        for (uint64_t k = 0; k < K; ++k) {
+            L->tstart[k] = L->ltstart[k];
+            const uint32_t tl = L->tlen[k];
+            if (tl == 0) continue;
+            uint32_t c = 16;
+            while (c < tl) c *= 2;
+            L->tcap[k] = c;
+            nt += tl;
+        }
+    L->n_entries = ne;
+    L->n_tokens = nt;
+    mark(4);
+    AGN_HIP(hipStreamSynchronize(st));
+    mark(5);
+    if (const char *t = AGN_KNOB("AGN_LOAD_TRACE"); t && t[0] == '1') {
+        const auto ms = [&](int i) {
+            return std::chrono::duration<double, std::milli>(tp[i + 1] - tp[i]).count();
+        };
+        std::fprintf(stderr,
+                     "oplog_load: %llu keys: index+scan %.3f, allocate %.3f, enqueue + records "
+                     "to the host %.3f, host fill %.3f, rest of the copy pass %.3f ms\n",
+                     (unsigned long long)K, ms(0), ms(1), ms(2), ms(3), ms(4));
+    }
+    return AGN_OK;
+}
+
+int agn_oplog_load(agn_oplog *L, const agn_log *src, void *stream) {
+    if (!L || !src) return fail(AGN_EINVAL, "oplog_load: null argument");
+    if (src->crdt_type != L->crdt || src->n_dcs != L->D || src->n_keys != L->K)
+        return fail(AGN_EINVAL, "oplog_load: type %u, %u DCs, %llu keys into a log of type %u, %u DCs, %llu keys",
+                    src->crdt_type, src->n_dcs, (unsigned long long)src->n_keys, L->crdt, L->D,
+                    (unsigned long long)L->K);
+    if ((src->oc_mask != nullptr) != L->sparse)
+        return fail(AGN_EINVAL, "oplog_load: oc_mask %s a %s log", src->oc_mask ? "into" : "missing for",
+                    L->sparse ? "sparse" : "dense");
+    if (!src->key_off || !src->oc || !src->op_id)
+        return fail(AGN_EINVAL, "oplog_load: key_off / oc / op_id required");
+    if (L->tags ? (!src->tag || !src->add_tok || !src->rem_off) : !src->eff)
+        return fail(AGN_EINVAL, "oplog_load: effect arrays missing for type %u", L->crdt);
+    int rc = use_device(L->ctx);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(L->wmu);
+    std::unique_lock<std::shared_mutex> x(L->rw);
+    rc = settle(L);
+    if (rc) return rc;
+    if (src->key_off == L->key_off || src->oc == L->a.oc || src->op_id == L->a.op_id)
+        return fail(AGN_EINVAL, "oplog_load: src is the log's own view");
+    agn_log s = *src;  // only the arrays of the log's type are read
+    s.key_type = nullptr;
+    s.key_id0 = nullptr;
+    s.key_mask = nullptr;
+    if (L->tags) {
+        s.eff = nullptr;
+    } else {
+        s.tag = nullptr;
+        s.add_tok = nullptr;
+        s.rem_off = nullptr;
+        s.rem_tok = nullptr;
+    }
+    return oplog_load_locked(L, s, (hipStream_t)stream);
 }
 
 int agn_oplog_key_meta(agn_oplog *L, uint64_t n, const uint64_t *keys, uint32_t *out_len,

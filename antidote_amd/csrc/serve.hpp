@@ -36,6 +36,34 @@ int oplog_prune_keys(agn_oplog *L, uint64_t n, const uint64_t *h_keys, const uin
                      const uint8_t *d_flags, const uint64_t *thr, const uint64_t *thr_mask,
                      hipStream_t st);
 
+// agn_oplog_load's device passes (oplog_load.hip).  The index pass writes one
+// record per key of `src` (device arrays [n_keys]; umask null unless the log
+// keeps key_mask, tslots null for a counter log) and ORs refusals into *bad:
+// 1 an invalid op id, 2 a length or ListLen beyond 32 bits, 4 removal tokens
+// without rem_tok.  slots / tslots: the slots of the key's segment and token
+// segment, then scanned in place (inclusive): with a zero word in front of
+// each, slots[k - 1] is key k's segment start and slots[n_keys - 1] the total.
+struct LoadIndex {
+    uint32_t *len, *tlen, *lcap, *id0, *last;
+    uint64_t *umask, *slots, *tslots;
+    uint32_t *bad;
+};
+size_t load_scan_bytes(uint64_t n_keys);  // scan scratch (0: sizing failed)
+int launch_load_index(const agn_log &src, uint32_t init_slots, const LoadIndex &o, void *scan_tmp,
+                      size_t scan_bytes, hipStream_t st);
+// Every key's entries from src into dst's arrays at entry slot lstart[k],
+// tokens at ltstart[k] (dst: the fresh arenas, no key arrays; ltstart null
+// for a counter log).
+int launch_load_copy(const agn_log &src, const agn_log &dst, uint64_t n_entries,
+                     const uint32_t *len, const uint32_t *tlen, const uint64_t *lstart,
+                     const uint64_t *ltstart, hipStream_t st);
+// The log's key arrays, and the live starts of the host's records (u32).
+int launch_load_keys(uint64_t K, const uint32_t *len, const uint32_t *id0, const uint32_t *lcap,
+                     const uint64_t *lstart, const uint64_t *ltstart, const uint64_t *umask,
+                     uint32_t *rec_lstart, uint32_t *rec_ltstart, uint64_t *key_off,
+                     uint64_t *key_len, uint32_t *key_id0, uint32_t *key_lcap,
+                     uint64_t *key_mask, hipStream_t st);
+
 }  // namespace agn
 
 namespace agn {

@@ -391,6 +391,13 @@ class OpLog:
         check(self.eng.lib.agn_oplog_flush(self.h, C.byref(v), stream), "agn_oplog_flush")
         return v
 
+    def load(self, dlog, stream=None):
+        """agn_oplog_load (recovery): a device log -- Engine.upload_log's or
+        agn_log_ingest's CSR, or another OpLog's flushed view -- into this
+        pristine log, device to device (blocks)."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        check(self.eng.lib.agn_oplog_load(self.h, C.byref(ls), stream), "agn_oplog_load")
+
     def prune(self, prune_ptr, thr_ptr, thr_mask_ptr=None, flags_ptr=None, stream=None):
         check(self.eng.lib.agn_oplog_prune(self.h, prune_ptr, thr_ptr, thr_mask_ptr, flags_ptr,
                                            stream), "agn_oplog_prune")

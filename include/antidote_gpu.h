@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define AGN_ABI_VERSION 6
+#define AGN_ABI_VERSION 7
 
 /* ---- status codes ------------------------------------------------------ */
 #define AGN_OK 0
@@ -401,6 +401,28 @@ int agn_oplog_gc_due(agn_oplog *log, uint64_t n, const uint64_t *keys, uint8_t *
  * one log (the consecutive-id index drops such keys by itself). */
 int agn_oplog_set_counter(agn_oplog *log, uint64_t n, const uint64_t *keys,
                           const uint32_t *counter);
+/* ABI v7.  Recovery (load_from_log, src/materializer_vnode.erl:288-319): loads
+ * the device log `src` -- CSR (key_len == NULL, e.g. agn_log_ingest's output)
+ * or segmented (key_len != NULL, e.g. another op log's flushed view, also after
+ * a prune; rem_off as the form requires) -- into `log`, device to device: no
+ * per-entry data crosses to the host, whose work is O(n_keys).  Afterwards the
+ * log is what agn_oplog_append would have made of the same entries key by key:
+ * op ids are src->op_id (equal neighbours are the parts of one op, as same_op;
+ * a gap is what agn_oplog_set_counter(k, id - 1) before the entry gives),
+ * counter[k] is the key's last id (0 for an empty key), ListLen is init_slots
+ * doubled up to the key's length, and key_id0 / key_mask / the GC trigger /
+ * the stats follow.  Segments are laid out tightly in key order, ListLen + 1
+ * slots per non-empty key, in arenas of exactly that size.  src->key_id0,
+ * key_mask and key_type are ignored.  Blocks until the load is done.
+ * AGN_EINVAL, the log untouched: crdt_type, n_dcs or n_keys differ from the
+ * log's; oc_mask is not present exactly when the log is sparse; an effect
+ * array of the log's type is missing; src is the log's own view; the log is
+ * not pristine (it holds an entry, staged or flushed, or a segment, or a
+ * key's counter is not 0); within a key an op id is 0, AGN_ID0_NONE or
+ * smaller than its predecessor (found on the device, before anything
+ * changes).  AGN_ENOTSUP, likewise untouched and before anything is
+ * allocated: the layout needs 2^32 slots or more. */
+int agn_oplog_load(agn_oplog *log, const agn_log *src, void *stream);
 /* Batched materialize/4 over the oplog's current contents (req / out as
  * agn_materialize, device pointers, req->keys indexing the oplog's keys).
  * Staged appends are flushed first (read-your-writes: update/2 is a
