@@ -148,6 +148,7 @@ PROTOTYPES = {
     "agn_state_capacity": (C.c_int, [C.POINTER(AgnLog), C.POINTER(AgnRead), P]),
     "agn_log_index_ids": (C.c_int, [P, C.POINTER(AgnLog), P, P]),
     "agn_log_index_masks": (C.c_int, [P, C.POINTER(AgnLog), P, P]),
+    "agn_log_index_pack": (C.c_int, [P, C.POINTER(AgnLog), P, P, P, C.POINTER(C.c_uint64), P]),
     "agn_tune": (C.c_int, [P, C.POINTER(AgnLog), C.POINTER(AgnRead), C.POINTER(AgnResult), P,
                            C.c_int, C.POINTER(C.c_int), P]),
     "agn_select_base": (C.c_int, [P, C.c_uint32, C.c_uint64, P, P, P, P, P, P, P, P]),

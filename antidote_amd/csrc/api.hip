@@ -174,6 +174,102 @@ static bool mixed_log(agn_ctx *ctx, const agn_log *log) {
     return false;
 }
 
+// ---- packed indexes (agn_log_index_pack) -----------------------------------
+// The last kPackIdx registered, keyed by (oc, key_off, n_entries, n_keys).
+// The table sits beside agn_ctx::mi in style (a mutex, a fixed array, an
+// atomic in front) but belongs to the process: the launchers that consult it
+// (launch_quad2, through agn_materialize, agn_tune and the op log's reads)
+// carry no context, and device pointers are unique across the process.  Each
+// entry is owned by the context that registered it, which drops it at
+// agn_close.  No result depends on the table: a log that is not found reads
+// oc.  g_pk_live in front: an agn_materialize while nothing is registered
+// pays one relaxed load.
+namespace {
+struct PackEnt {
+    agn_ctx *ctx;  // owner; nullptr = free slot
+    const uint64_t *oc, *key_off;
+    uint64_t n_entries, n_keys, seq;
+    PackIdx idx;
+    bool owned;  // agn_gen_dev's buffers: freed with the entry
+};
+constexpr int kPackIdx = 16;
+std::mutex g_pk_mu;
+PackEnt g_pk[kPackIdx] = {};
+uint64_t g_pk_seq = 0;
+std::atomic<int> g_pk_live{0};
+
+void pack_drop_locked(PackEnt &e) {
+    if (!e.ctx) return;
+    if (e.owned) {
+        (void)hipFree((void *)e.idx.rows);
+        (void)hipFree((void *)e.idx.base);
+        (void)hipFree((void *)e.idx.ok);
+    }
+    e = {};
+    g_pk_live.fetch_sub(1, std::memory_order_release);
+}
+
+bool pack_match(const PackEnt &e, const agn_log &log) {
+    return e.ctx && e.oc == log.oc && e.key_off == log.key_off && e.n_entries == log.n_entries &&
+           e.n_keys == log.n_keys;
+}
+
+// Drop the log's entry, if any.
+void pack_unregister(const agn_log &log) {
+    if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (pack_match(e, log)) pack_drop_locked(e);
+}
+
+// Replace the log's entry, else take a free slot, else evict the oldest.
+void pack_register(agn_ctx *ctx, const agn_log &log, const PackIdx &idx, bool owned) {
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    PackEnt *slot = nullptr;
+    for (auto &e : g_pk)
+        if (pack_match(e, log)) slot = &e;
+    for (auto &e : g_pk)
+        if (!slot && !e.ctx) slot = &e;
+    if (!slot) {
+        slot = &g_pk[0];
+        for (auto &e : g_pk)
+            if (e.seq < slot->seq) slot = &e;
+    }
+    pack_drop_locked(*slot);
+    *slot = {ctx, log.oc, log.key_off, log.n_entries, log.n_keys, ++g_pk_seq, idx, owned};
+    g_pk_live.fetch_add(1, std::memory_order_release);
+}
+
+// agn_close: the context's entries.
+void pack_clear(agn_ctx *ctx) {
+    if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (e.ctx == ctx) pack_drop_locked(e);
+}
+
+// agn_dev_free: an entry naming the freed allocation is stale.
+void pack_forget(const void *p) {
+    if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (e.ctx && (p == e.oc || p == e.key_off || p == e.idx.rows || p == e.idx.base ||
+                      p == e.idx.ok))
+            pack_drop_locked(e);
+}
+}  // namespace
+
+bool pack_lookup(const agn_log &log, PackIdx *out) {
+    if (g_pk_live.load(std::memory_order_relaxed) == 0) return false;
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (const auto &e : g_pk)
+        if (pack_match(e, log)) {
+            *out = e.idx;
+            return true;
+        }
+    return false;
+}
+
 static int validate(const agn_log *log, const agn_read *req, const agn_result *out) {
     if (!log || !req || !out) return fail(AGN_EINVAL, "null descriptor");
     // byte arrays are read by the kernels as aligned dwords (scalar loads
@@ -282,6 +378,7 @@ int agn_pool_trim(agn_ctx *ctx, uint64_t keep_bytes) {
 int agn_close(agn_ctx *ctx) {
     if (!ctx) return AGN_OK;
     agn_comm_destroy(ctx);
+    pack_clear(ctx);
     bool last = false;
     {
         std::lock_guard<std::mutex> g(g_pool_mu);
@@ -313,6 +410,7 @@ int agn_dev_alloc(agn_ctx *ctx, size_t bytes, void **out) {
 int agn_dev_free(agn_ctx *ctx, void *ptr) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    if (ptr) pack_forget(ptr);
     if (ptr) AGN_HIP(hipFree(ptr));
     return AGN_OK;
 }
@@ -423,6 +521,30 @@ int agn_log_index_masks(agn_ctx *ctx, const agn_log *log, uint64_t *out, void *s
     if (slot < 0) slot = (int)(ctx->mi_next++ % agn_ctx::kMaskIdx);
     ctx->mi[slot] = {out, log->n_keys, mixed};
     ctx->mi_any.store(true, std::memory_order_release);
+    return AGN_OK;
+}
+
+int agn_log_index_pack(agn_ctx *ctx, const agn_log *log, uint32_t *rows, uint64_t *base,
+                       uint8_t *ok, uint64_t *n_unpacked, void *stream) {
+    if (!log) return fail(AGN_EINVAL, "index_pack: null log");
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if (n_unpacked) *n_unpacked = 0;
+    if (!rows) {  // drop the log's registration
+        pack_unregister(*log);
+        return AGN_OK;
+    }
+    if (log->crdt_type != AGN_COUNTER_PN || log->n_dcs != 8 || log->oc_mask)
+        return fail(AGN_ENOTSUP, "index_pack: counter_pn logs with 8 dense DCs only");
+    if (!base || !ok) return fail(AGN_EINVAL, "index_pack: base / ok required");
+    if (log->n_keys && !log->key_off) return fail(AGN_EINVAL, "index_pack: key_off required");
+    if (log->n_entries && !log->oc) return fail(AGN_EINVAL, "index_pack: oc required");
+    // the kernels read rows / base as 16-byte units and ok as aligned dwords
+    if (((uintptr_t)rows | (uintptr_t)base | (uintptr_t)log->oc) & 15u || misaligned4(ok))
+        return fail(AGN_EINVAL, "index_pack: oc / rows / base 16-byte, ok 4-byte aligned");
+    rc = launch_index_pack(*log, rows, base, ok, n_unpacked, (hipStream_t)stream);
+    if (rc) return rc;
+    pack_register(ctx, *log, PackIdx{rows, base, ok}, false);
     return AGN_OK;
 }
 
@@ -1248,6 +1370,24 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
     // the consecutive-id index (ids 1..N per key), as an engine-built log carries it
     log->key_id0 = dmalloc<uint32_t>(K, err);
     if (!err && he == hipSuccess && K) err = launch_index_ids(*log, (uint32_t *)log->key_id0, s);
+    // and the packed index of a counter_pn D = 8 log (agn_log_index_pack), owned
+    // by the context; a failed allocation leaves the log without one
+    if (!err && he == hipSuccess && !tags && D == 8 && E) {
+        void *pr = nullptr, *pb = nullptr, *po = nullptr;
+        if (hipMalloc(&pr, E * 8 * sizeof(uint32_t)) == hipSuccess &&
+            hipMalloc(&pb, K * 8 * sizeof(uint64_t)) == hipSuccess &&
+            hipMalloc(&po, (K + 3) / 4 * 4) == hipSuccess &&
+            launch_index_pack(*log, (uint32_t *)pr, (uint64_t *)pb, (uint8_t *)po, nullptr, s) ==
+                AGN_OK) {
+            pack_register(ctx, *log, PackIdx{(uint32_t *)pr, (uint64_t *)pb, (uint8_t *)po}, true);
+        } else {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s);
+            if (pr) (void)hipFree(pr);
+            if (pb) (void)hipFree(pb);
+            if (po) (void)hipFree(po);
+        }
+    }
     (void)hipStreamSynchronize(s);
     (void)hipFree(scratch);
     if (he != hipSuccess) err = fail(AGN_EHIP, "k_gen: %s", hipGetErrorString(he));
@@ -1258,6 +1398,7 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
 int agn_gen_free_dev(agn_ctx *ctx, agn_log *log, agn_read *req) {
     int rc = use_device(ctx);
     if (rc) return rc;
+    if (log) pack_unregister(*log);  // frees the index agn_gen_dev built
     const void *ptrs[] = {log ? log->key_off : nullptr, log ? log->key_type : nullptr,
                           log ? log->oc : nullptr, log ? log->oc_mask : nullptr,
                           log ? log->op_id : nullptr, log ? log->txid : nullptr,

@@ -308,6 +308,20 @@ int launch_counter(const agn_log &log, const agn_read &req, const agn_result &ou
                    hipStream_t s);
 int launch_index_ids(const agn_log &log, uint32_t *out, hipStream_t st);
 int launch_index_masks(const agn_log &log, uint64_t *out, uint64_t *mixed, hipStream_t st);
+// The packed index of a log (agn_log_index_pack): u32 deltas [n_entries][8],
+// column bases [n_keys][8], packed flag [n_keys].
+struct PackIdx {
+    const uint32_t *rows;
+    const uint64_t *base;
+    const uint8_t *ok;
+};
+// n_unpacked (optional): the count of unpacked keys, read back (blocks).
+int launch_index_pack(const agn_log &log, uint32_t *rows, uint64_t *base, uint8_t *ok,
+                      uint64_t *n_unpacked, hipStream_t st);
+// The index registered for this log (api.hip; the launchers carry no
+// context, so the table is the process's, each entry owned by a context);
+// *out is written only when one is found.
+bool pack_lookup(const agn_log &log, PackIdx *out);
 int launch_counter_dense(const agn_log &log, const agn_read &req, const agn_result &out,
                          hipStream_t s);
 int tune_counter_dense(const agn_log &log, const agn_read &req, const agn_result &out,

@@ -446,6 +446,77 @@ __device__ __forceinline__ void q8_fold_eff(uint64_t incl, int64_t ev, uint64_t 
     sum += (mine && !badv) ? ev : 0;
 }
 
+// ---- packed rows (agn_log_index_pack; D = 8, cold dense reads) -------------
+// A key's OpSSCommit rows as u32 deltas against the key's column minima
+// (pack_base[key][d]): 32 bytes per op instead of 64.  A 64-op chunk is 2 KiB,
+// two lane-contiguous 16-byte loads: lane l of load j holds DCs 4p .. 4p+3
+// (p = l & 1) of op 32 j + (l >> 1).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+struct P8Rows {
+    u32x4 x[2];
+};
+
+template <bool NT>
+__device__ __forceinline__ P8Rows p8_load_rows(const uint32_t *__restrict__ rows, uint64_t off,
+                                               uint64_t b, uint64_t n_entries) {
+    const int lane = lane_id();
+    const u32x4 *r = reinterpret_cast<const u32x4 *>(rows);
+    const uint64_t lim = n_entries * 2u - 1u;
+    P8Rows c;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        uint64_t u = (off + b) * 2u + (uint64_t)(j * AGN_WAVE + lane);
+        u = u < lim ? u : lim;  // past the log's end: clamped, masked in p8_verdict
+        c.x[j] = ld<NT>(r + u);
+    }
+    return c;
+}
+
+// Bit q of the result = some bit of pair q of b (q = 0..31), on the scalar
+// unit: nib_any16 for a ballot whose 2 lanes per op are its 2 parts.
+__device__ __forceinline__ uint64_t pair_any32(uint64_t b) {
+    b = (b | (b >> 1)) & 0x5555555555555555ull;
+    b = (b | (b >> 1)) & 0x3333333333333333ull;
+    b = (b | (b >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    b = (b | (b >> 4)) & 0x00FF00FF00FF00FFull;
+    b = (b | (b >> 8)) & 0x0000FFFF0000FFFFull;
+    return (b | (b >> 16)) & 0xFFFFFFFFull;
+}
+
+// q8_verdict<false> over packed rows.  thr: this lane's four columns of
+// R - pack_base, saturated to 2^32 - 1 -- oc = base + delta <= R iff
+// delta <= R - base; noR: R is below the base in some column, so every op is
+// excluded.  mx: the lane's running maxima of the included ops' deltas (the
+// LastOpCt of the cold read is base + max delta, folded after the key).
+__device__ __forceinline__ uint64_t p8_verdict(const P8Rows &c, uint64_t b, uint64_t n,
+                                               const u32x4 &thr, bool noR, u32x4 &mx,
+                                               uint32_t &cnt, int64_t &first_excl) {
+    const int q = lane_id() >> 1;
+    const uint64_t valid = (n - b >= (uint64_t)AGN_WAVE) ? ~0ull : ((1ull << (n - b)) - 1ull);
+    uint64_t bad = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const u32x4 d = c.x[j];
+        bad |= pair_any32(ballot(d.x > thr.x || d.y > thr.y || d.z > thr.z || d.w > thr.w))
+               << (32 * j);
+    }
+    if (noR) bad = ~0ull;
+    const uint64_t incl = valid & ~bad, excl = valid & bad;
+    if (first_excl < 0 && excl) first_excl = (int64_t)b + (int64_t)__builtin_ctzll(excl);
+    cnt += (uint32_t)__builtin_popcountll(incl);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const bool in = ((incl >> (32 * j + q)) & 1ull) != 0ull;
+        const u32x4 d = c.x[j];
+        mx.x = (in && d.x > mx.x) ? d.x : mx.x;
+        mx.y = (in && d.y > mx.y) ? d.y : mx.y;
+        mx.z = (in && d.z > mx.z) ? d.z : mx.z;
+        mx.w = (in && d.w > mx.w) ? d.w : mx.w;
+    }
+    return incl;
+}
+
 // scan_key for D = 8 with lane-CONTIGUOUS row loads ("quad rows"): load j of a
 // 64-op chunk reads bytes [1 KiB j, 1 KiB (j+1)) of the chunk's rows, so
 // every instruction covers 8 whole 128-byte lines -- the row-per-lane loads

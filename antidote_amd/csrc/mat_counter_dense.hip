@@ -611,7 +611,29 @@ __device__ __forceinline__ void q2_side(Q2Key &k, const DenseArgs &a, const Mask
     q2_apply<ANY_WARM, MSK>(k, a, mk, x, kmw, key_type, sct, sct_ignore, req_txid);
 }
 
-template <bool ANY_WARM, bool MSK>
+// A request's share of the packed index: the key's pack_ok byte (scalar
+// cache) and pack_base at this lane's DCs 2p, 2p+1 (p = lane & 3), the
+// layout of R in Q2Key -- one 16-byte vector load, as q2_load's of R and for
+// its reason: as 8 uniform words per key next to the kernel's pointer
+// arguments the base rows would push scalar state out to VGPR lanes.  Both
+// addresses need only the key id: they share R's round trip.  bq stays in
+// registers to the LastOpCt fold (the packed rows take 8 VGPRs per key where
+// the quad rows take 16).
+struct Q2Pack {
+    u64x2 bq;
+    uint32_t ok;  // the pack_ok byte
+};
+
+__device__ __forceinline__ Q2Pack q2_pack_load(const Q2Key &k, const uint64_t *__restrict__ base,
+                                               const uint8_t *__restrict__ ok) {
+    Q2Pack p;
+    p.ok = ldc_byte(ok, k.key);
+    p.bq = *reinterpret_cast<const u64x2 *>(base + k.key * 8u + 2u * (uint64_t)(lane_id() & 3));
+    return p;
+}
+
+// PACK: the request's share of the packed index loads with the rest (pk).
+template <bool ANY_WARM, bool MSK, bool PACK = false>
 __device__ __forceinline__ Q2Key q2_prologue(const DenseArgs &a, const MaskArgs &mk, uint64_t i,
                                              const uint64_t *__restrict__ keys,
                                              const uint64_t *__restrict__ key_off,
@@ -621,9 +643,13 @@ __device__ __forceinline__ Q2Key q2_prologue(const DenseArgs &a, const MaskArgs 
                                              const uint64_t *__restrict__ R,
                                              const uint64_t *__restrict__ sct,
                                              const uint8_t *__restrict__ sct_ignore,
-                                             const uint64_t *__restrict__ req_txid) {
+                                             const uint64_t *__restrict__ req_txid,
+                                             const uint64_t *__restrict__ pack_base = nullptr,
+                                             const uint8_t *__restrict__ pack_ok = nullptr,
+                                             Q2Pack *pk = nullptr) {
     Q2Key k;
     q2_meta(k, i, keys, key_off, key_len, key_id0);
+    if constexpr (PACK) *pk = q2_pack_load(k, pack_base, pack_ok);
     const uint64_t kmw = MSK ? key_word(mk, k.key, key_off) : 0ull;
     q2_side<ANY_WARM, MSK>(k, a, mk, kmw, key_off, key_type, R, sct, sct_ignore, req_txid);
     return k;
@@ -942,6 +968,62 @@ __device__ __forceinline__ MaskArgs mask_of(const T &x) {
     return MaskArgs{x.key_mask, x.oc_mask, x.R_mask, x.sct_mask, x.o_mask};
 }
 
+// k_counter_quad2's parameters past Q2Params' (its PACK form): the packed index
+// of the log (agn_log_index_pack), read from the kernarg segment where used.
+struct Q2PackParams {
+    DenseArgs a;
+    MaskArgs mk;
+    const void *args[20];  // keys .. o_err
+    const uint32_t *rows;
+    const uint64_t *base;
+    const uint8_t *ok;
+};
+static_assert(offsetof(Q2PackParams, rows) == offsetof(Q2Params, list),
+              "Q2PackParams follows k_counter_quad2's parameter list");
+
+// p8_verdict's thresholds: R - base per column, saturated, moved from the
+// lanes that hold DCs 2p', 2p'+1 (p' = lane & 3) to the packed layout -- lane
+// l compares DCs 4p .. 4p+3 (p = l & 1), held by lanes 2p and 2p+1 of its
+// quad.  noR: R < base in some column.
+__device__ __forceinline__ u32x4 q2_pack_thr(const Q2Key &k, const Q2Pack &p, bool &noR) {
+    noR = ballot(k.rA < p.bq.x || k.rB < p.bq.y) != 0ull;
+    const uint64_t dA = k.rA - p.bq.x, dB = k.rB - p.bq.y;
+    const uint32_t tA = (dA >> 32) ? 0xFFFFFFFFu : (uint32_t)dA;
+    const uint32_t tB = (dB >> 32) ? 0xFFFFFFFFu : (uint32_t)dB;
+    u32x4 t;
+    t.x = __builtin_amdgcn_update_dpp(0u, tA, 0x88, 0xF, 0xF, false);  // quad_perm 0,2,0,2
+    t.y = __builtin_amdgcn_update_dpp(0u, tB, 0x88, 0xF, 0xF, false);
+    t.z = __builtin_amdgcn_update_dpp(0u, tA, 0xDD, 0xF, 0xF, false);  // quad_perm 1,3,1,3
+    t.w = __builtin_amdgcn_update_dpp(0u, tB, 0xDD, 0xF, 0xF, false);
+    return t;
+}
+
+// LastOpCt of a cold read over packed rows (q2_ctfold's place): the lanes'
+// delta maxima fold by xor-shuffles over strides 2 .. 32 (even lanes then hold
+// DCs 0-3, odd lanes DCs 4-7), go back to the lanes of DCs 2p', 2p'+1, and
+// ct = base + max delta when an op was included, else SCT's value: 0, cold.
+__device__ __forceinline__ void q2_pack_ct(const Q2Pack &p, u32x4 mx, Q2Acc &s) {
+#pragma unroll
+    for (int x = 2; x < AGN_WAVE; x <<= 1) {
+        const uint32_t a = (uint32_t)__shfl_xor((int)mx.x, x, AGN_WAVE);
+        const uint32_t b = (uint32_t)__shfl_xor((int)mx.y, x, AGN_WAVE);
+        const uint32_t c = (uint32_t)__shfl_xor((int)mx.z, x, AGN_WAVE);
+        const uint32_t d = (uint32_t)__shfl_xor((int)mx.w, x, AGN_WAVE);
+        mx.x = a > mx.x ? a : mx.x;
+        mx.y = b > mx.y ? b : mx.y;
+        mx.z = c > mx.z ? c : mx.z;
+        mx.w = d > mx.w ? d : mx.w;
+    }
+    // quad_perm 0,0,1,1: lanes p' = 0, 1 read the even lane's maxima, 2, 3 the odd lane's
+    const uint32_t g0 = __builtin_amdgcn_update_dpp(0u, mx.x, 0x50, 0xF, 0xF, false);
+    const uint32_t g1 = __builtin_amdgcn_update_dpp(0u, mx.y, 0x50, 0xF, 0xF, false);
+    const uint32_t g2 = __builtin_amdgcn_update_dpp(0u, mx.z, 0x50, 0xF, 0xF, false);
+    const uint32_t g3 = __builtin_amdgcn_update_dpp(0u, mx.w, 0x50, 0xF, 0xF, false);
+    const bool hi = (lane_id() & 1) != 0;
+    s.ctA = s.cnt ? p.bq.x + (uint64_t)(hi ? g2 : g0) : 0ull;
+    s.ctB = s.cnt ? p.bq.y + (uint64_t)(hi ? g3 : g1) : 0ull;
+}
+
 // The dense warm form runs at 6 waves per SIMD: 80 VGPRs and 2 scratch
 // spills instead of 84 VGPRs (5 waves) and 24 spilled SGPRs, 8.13 against
 // 8.33 ms on warm cfg2 (profiles/r05/ab_quad2_w6.log).  The masked forms spill
@@ -960,7 +1042,12 @@ __device__ __forceinline__ MaskArgs mask_of(const T &x) {
 // Both forms serve the pairs whose two keys fit one chunk; a pair with a
 // longer key (or, masked, a mixed one) runs the kernel as it was before
 // either, and so does every pair when both are 0.
-template <bool ANY_WARM, bool MSK, bool Q2_EFF, bool Q2_STORE>
+//
+// PACK (cold dense, with both forms above): the log carries a packed index
+// (agn_log_index_pack) and the straight path scans its 32-byte rows -- a pair
+// whose two keys fit one chunk and are both packed (pack_ok).  Every other
+// pair reads oc in the code below, as the kernel without an index does.
+template <bool ANY_WARM, bool MSK, bool Q2_EFF, bool Q2_STORE, bool PACK = false>
 __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad2(
     DenseArgs a, MaskArgs mk, const uint64_t *__restrict__ keys,
     const uint64_t *__restrict__ key_off, const uint64_t *__restrict__ key_len,
@@ -972,16 +1059,22 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
     const int64_t *__restrict__ base_value, int64_t *__restrict__ o_value,
     int64_t *__restrict__ o_hole, uint64_t *__restrict__ o_lastct,
     uint32_t *__restrict__ o_count, uint32_t *__restrict__ o_flags,
-    uint32_t *__restrict__ o_err) {
+    uint32_t *__restrict__ o_err, const uint32_t *__restrict__ pack_rows,
+    const uint64_t *__restrict__ pack_base, const uint8_t *__restrict__ pack_ok) {
+    static_assert(!PACK || (!ANY_WARM && !MSK && Q2_EFF && Q2_STORE),
+                  "packed rows: the cold dense form only");
     const uint32_t blk = block_order(a.xcd, blockIdx.x, gridDim.x);
     const uint64_t i0 = uniform_u64((uint64_t)blk * 2u);
     if (i0 >= a.n_req) return;
     const bool two = i0 + 1u < a.n_req;
     const uint64_t i1 = two ? i0 + 1u : i0;
-    const Q2Key k0 = q2_prologue<ANY_WARM, MSK>(a, mk, i0, keys, key_off, key_len, key_type,
-                                                key_id0, R, sct, sct_ignore, req_txid);
-    const Q2Key k1 = q2_prologue<ANY_WARM, MSK>(a, mk, i1, keys, key_off, key_len, key_type,
-                                                key_id0, R, sct, sct_ignore, req_txid);
+    Q2Pack pk0{}, pk1{};
+    const Q2Key k0 = q2_prologue<ANY_WARM, MSK, PACK>(a, mk, i0, keys, key_off, key_len, key_type,
+                                                      key_id0, R, sct, sct_ignore, req_txid,
+                                                      pack_base, pack_ok, &pk0);
+    const Q2Key k1 = q2_prologue<ANY_WARM, MSK, PACK>(a, mk, i1, keys, key_off, key_len, key_type,
+                                                      key_id0, R, sct, sct_ignore, req_txid,
+                                                      pack_base, pack_ok, &pk1);
     Q2Acc s0, s1;
     s0.ctA = k0.eA;
     s0.ctB = k0.eB;
@@ -993,11 +1086,35 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
         // loop's exit the effects were waited for before the folds).  Any
         // other pair runs the code below, as before.
         const bool one = k0.n <= (uint64_t)AGN_WAVE && k1.n <= (uint64_t)AGN_WAVE;
-        if (a.n_entries != 0 && one && (!MSK || (k0.uni && k1.uni))) {
+        if (a.n_entries != 0 && one && (!MSK || (k0.uni && k1.uni)) &&
+            (!PACK || (pk0.ok & pk1.ok) != 0u)) {
             const bool d0 = !k0.corrupt, d1 = !k1.corrupt;
             uint64_t in0 = 0, in1 = 0;  // chunk 0's included ops
             int64_t ev0 = 0, ev1 = 0;   // and their effects (lane = op)
-            if constexpr (Q2_EFF) {
+            u32x4 m0 = {0u, 0u, 0u, 0u}, m1 = {0u, 0u, 0u, 0u};  // PACK: maxima of included deltas
+            if constexpr (PACK) {
+                const uint32_t *const rows = kparams<Q2PackParams>().rows;
+                const P8Rows c0 = p8_load_rows<true>(rows, k0.off, 0, a.n_entries);
+                const P8Rows c1 = p8_load_rows<true>(rows, k1.off, 0, a.n_entries);
+                // eff and R (the effect loads' dummy rows) are read here, under the
+                // rows, as the result pointers below and for their reason
+                const int64_t *const l_eff = (const int64_t *)kparams<Q2Params>().eff;
+                const uint64_t *const l_R = (const uint64_t *)kparams<Q2Params>().R;
+                __builtin_amdgcn_sched_barrier(0);
+                bool nr0, nr1;
+                const u32x4 th0 = q2_pack_thr(k0, pk0, nr0), th1 = q2_pack_thr(k1, pk1, nr1);
+                // unconditional verdicts, dropped for a corrupt key (see below)
+                Q2Acc t0 = s0, t1 = s1;
+                in0 = p8_verdict(c0, 0, k0.n, th0, nr0, m0, t0.cnt, t0.first_excl);
+                in0 = d0 ? in0 : 0ull;
+                if (d0) s0 = t0;
+                ev0 = q8_load_eff(l_eff, k0.off, 0, in0, reinterpret_cast<const int64_t *>(l_R + k0.i * 8u));
+                in1 = p8_verdict(c1, 0, k1.n, th1, nr1, m1, t1.cnt, t1.first_excl);
+                in1 = d1 ? in1 : 0ull;
+                if (d1) s1 = t1;
+                ev1 = q8_load_eff(l_eff, k1.off, 0, in1, reinterpret_cast<const int64_t *>(l_R + k1.i * 8u));
+                __builtin_amdgcn_sched_barrier(0);  // both effect loads are in flight from here
+            } else if constexpr (Q2_EFF) {
                 const Q8Rows c0 = q8_load_rows<true>(oc, k0.off, 0, a.n_entries);
                 const Q8Rows c1 = q8_load_rows<true>(oc, k1.off, 0, a.n_entries);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1032,8 +1149,13 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
             int64_t *const l_value = pr.o_value, *const l_hole = pr.o_hole;
             uint64_t *const l_lastct = pr.o_lastct;
             uint32_t *const l_count = pr.o_count, *const l_flags = pr.o_flags, *const l_err = pr.o_err;
-            q2_ctfold<MSK>(k0, s0);
-            q2_ctfold<MSK>(k1, s1);
+            if constexpr (PACK) {
+                q2_pack_ct(pk0, m0, s0);
+                q2_pack_ct(pk1, m1, s1);
+            } else {
+                q2_ctfold<MSK>(k0, s0);
+                q2_ctfold<MSK>(k1, s1);
+            }
             if constexpr (Q2_EFF) {
                 __builtin_amdgcn_sched_barrier(0);  // the wait for the effects: after the folds
                 q8_fold_eff(in0, ev0, 0, s0.sum, s0.first_err);
@@ -1051,6 +1173,34 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
             }
             return;
         }
+    }
+    if constexpr (PACK) {
+        // A pair the packed rows do not serve (a key longer than a chunk or not
+        // packed, an empty log) reads oc one request after the other, each from
+        // its own prologue on (scalar-cache hits) and with every pointer from
+        // the kernarg segment: kept side by side as below, the two requests'
+        // scan state costs the straight path a wave per SIMD.  No TxIds are
+        // passed: a cold read includes an op whatever its TxId (nip is all
+        // ones).  Same functions, same results as the form without an index.
+#pragma nounroll
+        for (uint32_t h = 0; h < (two ? 2u : 1u); ++h) {
+            const auto &p = kparams<Q2Params>();
+            const Q2Key k = q2_prologue<ANY_WARM, MSK>(a, mk, i0 + h, p.keys, p.key_off, p.key_len,
+                                                       p.key_type, p.key_id0, p.R, p.sct,
+                                                       p.sct_ignore, p.req_txid);
+            Q2Acc s;
+            s.ctA = k.eA;
+            s.ctB = k.eB;
+            if (a.n_entries != 0 && !k.corrupt)
+                scan_key_q8<false, true, false, false>(p.oc, p.eff, nullptr, 0ull, k.off, k.n,
+                                                       a.n_entries, k.rA, k.rB, k.sA, k.sB, s.ctA,
+                                                       s.ctB, s.sum, s.cnt, s.first_excl,
+                                                       s.first_err, k.noR);
+            const auto &pe = kparams<Q2Params>();
+            q2_epilogue<MSK>(k, s, a.hints, pe.op_id, pe.base_value, pe.o_value, pe.o_hole,
+                             pe.o_lastct, pe.o_count, pe.o_flags, pe.o_err, mk.o_mask);
+        }
+        return;
     }
     if (a.n_entries != 0) {
         const Q8Chunk c0 = q8_load<true, false>(oc, eff, k0.off, 0, a.n_entries);
@@ -1291,12 +1441,14 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
     const uint64_t nb = (req.n_req + 1) / 2;
     if (nb > 0x7fffffffull) return fail(AGN_EINVAL, "batch too large: %llu requests",
                                         (unsigned long long)req.n_req);
-#define AGN_Q2L_(W, M, E, S)                                                                    \
-    hipLaunchKernelGGL((k_counter_quad2<W, M, E, S>), dim3((unsigned)nb), dim3(64), 0, st, a,   \
+    PackIdx pk{};
+#define AGN_Q2L_(W, M, E, S, ...)                                                               \
+    hipLaunchKernelGGL((k_counter_quad2<W, M, E, S, ##__VA_ARGS__>), dim3((unsigned)nb),        \
+                       dim3(64), 0, st, a,                                                      \
                        mk, req.keys, log.key_off, log.key_len, log.key_type, id0_index(log),    \
                        log.oc, log.op_id, log.eff, log.txid, req.R, req.sct, req.sct_ignore,    \
                        req.txid, req.base_value, out.value, out.hole, out.lastct, out.count,    \
-                       out.flags, out.err_pos)
+                       out.flags, out.err_pos, pk.rows, pk.base, pk.ok)
 #define AGN_Q2L(W, M)                                                                           \
     do {                                                                                        \
         if (q2e && q2s) AGN_Q2L_(W, M, true, true);                                             \
@@ -1323,7 +1475,15 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
     const uintptr_t a8 = (uintptr_t)out.count | (uintptr_t)out.flags | (uintptr_t)out.err_pos;
     const bool q2s = ((sv && (sv[0] == '0' || sv[0] == '1')) ? sv[0] == '1' : dflt) &&
                      (a16 & 15u) == 0 && (a8 & 7u) == 0;
-    if (req.sct) {
+    // AGN_Q2_PACK = 0|1 (A/B knob, default on): a cold dense batch over a log
+    // with a registered packed index (agn_log_index_pack) scans its 32-byte
+    // rows.  The PACK form has both forms above, so it needs both in effect.
+    const char *pv = AGN_KNOB("AGN_Q2_PACK");
+    const bool pack = dflt && q2e && q2s && log.n_entries != 0 && !(pv && pv[0] == '0') &&
+                      pack_lookup(log, &pk);
+    if (pack) {
+        AGN_Q2L_(false, false, true, true, true);
+    } else if (req.sct) {
         if (msk) AGN_Q2L(true, true);
         else AGN_Q2L(true, false);
     } else {
@@ -1622,7 +1782,123 @@ __global__ __launch_bounds__(256) void k_index_ids(const uint64_t *__restrict__ 
     if (lane == 0) out[k] = ok ? (uint32_t)id0 : AGN_ID0_NONE;
 }
 
+// agn_log_index_pack (D = 8): one wave per key.  Pass 1 takes the segment's
+// column minima and maxima (lane = entry), pass 2 writes the u32 deltas of a
+// key whose every column spans at most 2^32 - 1 -- lane-contiguous 16-byte
+// stores in the layout p8_load_rows reads: lane l of store j holds DCs
+// 4p .. 4p+3 (p = l & 1) of entry 32 j + (l >> 1).  An empty key is packed
+// with an all-zero base.  The block's unpacked keys are counted as
+// k_index_masks counts its mixed ones.
+__global__ __launch_bounds__(256) void k_index_pack(const uint64_t *__restrict__ key_off,
+                                                   const uint64_t *__restrict__ key_len,
+                                                   const uint64_t *__restrict__ oc,
+                                                   uint64_t n_keys, uint32_t *__restrict__ rows,
+                                                   uint64_t *__restrict__ base,
+                                                   uint8_t *__restrict__ ok,
+                                                   unsigned long long *__restrict__ unpacked) {
+    constexpr int D = 8;
+    __shared__ uint32_t blk_un;
+    if (threadIdx.x == 0) blk_un = 0;
+    __syncthreads();
+    const uint64_t k = uniform_u64((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6));
+    const int lane = lane_id();
+    if (k < n_keys) {
+        const uint64_t off = key_off[k];
+        const uint64_t n = key_len ? key_len[k] : key_off[k + 1] - off;
+        uint64_t mn[D], mx[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            mn[d] = ~0ull;
+            mx[d] = 0ull;
+        }
+        for (uint64_t b = 0; b < n; b += AGN_WAVE) {
+            const uint64_t p = b + (uint64_t)lane;
+            if (p < n) {
+                uint64_t o[D];
+                load_row<D, false>(oc + (off + p) * D, o);
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    mn[d] = o[d] < mn[d] ? o[d] : mn[d];
+                    mx[d] = umax64(mx[d], o[d]);
+                }
+            }
+        }
+        bool fits = true;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+#pragma unroll
+            for (int x = 1; x < AGN_WAVE; x <<= 1) {
+                const uint64_t a = shfl_xor_u64(mn[d], x);
+                mn[d] = a < mn[d] ? a : mn[d];
+                mx[d] = umax64(mx[d], shfl_xor_u64(mx[d], x));
+            }
+            if (n == 0) mn[d] = 0ull;
+            fits = fits && (n == 0 || mx[d] - mn[d] <= 0xFFFFFFFFull);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) base[k * D + d] = mn[d];
+            ok[k] = fits ? 1 : 0;
+            if (!fits) atomicAdd(&blk_un, 1u);
+        }
+        if (fits) {
+            const bool hi = (lane & 1) != 0;
+            const uint64_t b0 = hi ? mn[4] : mn[0], b1 = hi ? mn[5] : mn[1];
+            const uint64_t b2 = hi ? mn[6] : mn[2], b3 = hi ? mn[7] : mn[3];
+            for (uint64_t b = 0; b < n; b += AGN_WAVE / 2) {
+                const uint64_t p = b + (uint64_t)(lane >> 1);
+                if (p < n) {
+                    const uint64_t u = (off + p) * 2u + (hi ? 1u : 0u);  // 16-byte unit of rows
+                    const u64x2 *src = reinterpret_cast<const u64x2 *>(oc) + u * 2u;
+                    const u64x2 lo = src[0], hh = src[1];
+                    u32x4 v;
+                    v.x = (uint32_t)(lo.x - b0);
+                    v.y = (uint32_t)(lo.y - b1);
+                    v.z = (uint32_t)(hh.x - b2);
+                    v.w = (uint32_t)(hh.y - b3);
+                    reinterpret_cast<u32x4 *>(rows)[u] = v;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && blk_un && unpacked)
+        atomicAdd(&unpacked[(blockIdx.x % IM_CNT) * IM_STRIDE], (unsigned long long)blk_un);
+}
+
 }  // namespace
+
+int launch_index_pack(const agn_log &log, uint32_t *rows, uint64_t *base, uint8_t *ok,
+                      uint64_t *n_unpacked, hipStream_t st) {
+    const uint64_t nb = (log.n_keys + 3) / 4;
+    if (n_unpacked) *n_unpacked = 0;
+    if (nb == 0) return AGN_OK;
+    if (nb > 0x7fffffffull) return fail(AGN_EINVAL, "index_pack: too many keys");
+    unsigned long long *cnt = nullptr;
+    const size_t cb = (size_t)IM_CNT * IM_STRIDE * sizeof(unsigned long long);
+    if (n_unpacked) {
+        AGN_HIP(pool_malloc(&cnt, cb, st));
+        if (hipMemsetAsync(cnt, 0, cb, st) != hipSuccess) {
+            (void)hipFreeAsync(cnt, st);
+            return fail(AGN_EHIP, "index_pack: counter reset");
+        }
+    }
+    hipLaunchKernelGGL(k_index_pack, dim3((unsigned)nb), dim3(256), 0, st, log.key_off,
+                       log.key_len, log.oc, log.n_keys, rows, base, ok, cnt);
+    int rc = hipGetLastError() == hipSuccess ? AGN_OK : fail(AGN_EHIP, "index_pack: launch");
+    if (cnt) {
+        // the count is read back here: the call blocks until the index is built
+        std::vector<unsigned long long> h((size_t)IM_CNT * IM_STRIDE);
+        if (rc == AGN_OK &&
+            (hipMemcpyAsync(h.data(), cnt, cb, hipMemcpyDeviceToHost, st) != hipSuccess ||
+             hipStreamSynchronize(st) != hipSuccess))
+            rc = fail(AGN_EHIP, "index_pack: unpacked-key count");
+        if (rc == AGN_OK)
+            for (uint32_t i = 0; i < IM_CNT; ++i) *n_unpacked += h[(size_t)i * IM_STRIDE];
+        (void)hipFreeAsync(cnt, st);
+    }
+    return rc;
+}
 
 int launch_index_masks(const agn_log &log, uint64_t *out, uint64_t *mixed, hipStream_t st) {
     const uint64_t nb = (log.n_keys + 3) / 4;

@@ -137,6 +137,29 @@ class Engine:
             dlog.bufs["key_mask"] = b
         return b
 
+    def index_pack(self, dlog, stream=None, count=True):
+        """Build and register the packed index of a device counter_pn log with
+        8 dense DCs (agn_log_index_pack); returns (rows, base, ok, n_unpacked)
+        -- the buffers are owned by dlog when dlog is DeviceArrays, n_unpacked
+        is None with count=False (no sync)."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        K, E = int(ls.n_keys), int(ls.n_entries)
+        rows, base = self.empty(max(1, E) * 32), self.empty(max(1, K) * 64)
+        ok = self.empty((K + 3) // 4 * 4)
+        n = C.c_uint64(0)
+        check(self.lib.agn_log_index_pack(self.ctx, C.byref(ls), rows.ptr, base.ptr, ok.ptr,
+                                          C.byref(n) if count else None, stream),
+              "agn_log_index_pack")
+        if isinstance(dlog, DeviceArrays):
+            dlog.bufs.update(pack_rows=rows, pack_base=base, pack_ok=ok)
+        return rows, base, ok, (n.value if count else None)
+
+    def drop_pack(self, dlog):
+        """Drop the log's packed-index registration (agn_log_index_pack, rows = NULL)."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        check(self.lib.agn_log_index_pack(self.ctx, C.byref(ls), None, None, None, None, None),
+              "agn_log_index_pack")
+
     def alloc_log_like(self, log: EncodedLog) -> DeviceArrays:
         """Device arrays with the sizes (and presence) of `log`'s (agn_prune_ops output)."""
         s = _abi.AgnLog()

@@ -304,6 +304,35 @@ int agn_log_index_ids(agn_ctx *ctx, const agn_log *log, uint32_t *out, void *str
  * were passed when more than 1/16 of the log's keys are mixed. */
 int agn_log_index_masks(agn_ctx *ctx, const agn_log *log, uint64_t *out, void *stream);
 
+/* The packed index of a device counter_pn log with n_dcs == 8 and no oc_mask:
+ * the OpSSCommit rows as u32 deltas against per-key column minima, half the
+ * bytes a cold read streams.  Log rows are immutable once appended, and clocks
+ * are microsecond timestamps, so a key's column rarely spans 2^32.
+ *   base[k][d] ([n_keys][8] u64) = min over key k's entries of oc[e][d]; all
+ *     zeros for an empty key;
+ *   ok[k] ([n_keys] u8, in an allocation of whole dwords) = 1 iff every column
+ *     of key k spans at most 2^32 - 1 (empty keys: 1);
+ *   rows[e][d] ([n_entries][8] u32) = oc[e][d] - base[k][d] for the entries of
+ *     keys with ok == 1, unspecified otherwise.
+ * The caller owns the three device buffers (rows and base 16-byte aligned, as
+ * oc must be; ok 4-byte aligned).  The call builds the index and registers it
+ * for the log -- the key is (oc, key_off, n_entries, n_keys) -- and a cold
+ * dense agn_materialize / agn_tune of that log then scans `rows` for every
+ * pair of requests whose keys are both packed and at most 64 entries long;
+ * every other read uses oc.  Results never depend on the index.  Like key_id0
+ * it must be rebuilt, or dropped, when entries change or the log is freed:
+ * rows == NULL drops the registration (nothing else is read then), and
+ * agn_dev_free of any of the arrays involved, agn_close and a 17th
+ * registration (the oldest goes) drop it too.  n_unpacked (may be NULL)
+ * receives the count of keys with ok == 0 and makes the call block; with
+ * NULL nothing is synchronized and the call may be captured.
+ * AGN_ENOTSUP: n_dcs != 8, oc_mask != NULL, not a counter_pn log;
+ * AGN_EINVAL: a missing or misaligned array.  Environment AGN_Q2_PACK=0
+ * keeps reads on oc (A/B knob).
+ * An addition to ABI v7: no struct changed, the version number stays. */
+int agn_log_index_pack(agn_ctx *ctx, const agn_log *log, uint32_t *rows, uint64_t *base,
+                       uint8_t *ok, uint64_t *n_unpacked, void *stream);
+
 /* Upper bound of live pairs per request for set/register types:
  * writes cap_off[n_req+1] (host pointers): cap = #adding entries of the key
  * + #base pairs.  Host-side helper (the bound is static per log): every
