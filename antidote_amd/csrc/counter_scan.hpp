@@ -517,6 +517,69 @@ __device__ __forceinline__ uint64_t p8_verdict(const P8Rows &c, uint64_t b, uint
     return incl;
 }
 
+// ---- four packed keys per wave (k_counter_pack4) ---------------------------
+// The wave's per-(key, DC) values -- R, pack_base, the thresholds, LastOpCt --
+// live one per lane in the "slot" layout the transposed fold below ends in:
+// lane l holds key g = l >> 4 and DC d = 4 (l & 1) + 2 ((l >> 3) & 1) +
+// ((l >> 2) & 1); bit 1 of the lane does not count (lanes l and l ^ 2 hold the
+// same slot).  p4_slot is the slot's index 8 g + d in a [4][8] row group.
+__device__ __forceinline__ int p4_slot(int lane) {
+    return ((lane >> 4) << 3) + ((lane & 1) << 2) + (((lane >> 3) & 1) << 1) + ((lane >> 2) & 1);
+}
+
+// p8_verdict's thresholds of key g from the slot layout: lane l compares DCs
+// 4p .. 4p+3 (p = l & 1), held by lanes 16 g + p + {0, 4, 8, 12}.
+__device__ __forceinline__ u32x4 p4_thr(uint32_t t, int g) {
+    const int src = 16 * g + (lane_id() & 1);
+    u32x4 th;
+    th.x = (uint32_t)__shfl((int)t, src, AGN_WAVE);
+    th.y = (uint32_t)__shfl((int)t, src + 4, AGN_WAVE);
+    th.z = (uint32_t)__shfl((int)t, src + 8, AGN_WAVE);
+    th.w = (uint32_t)__shfl((int)t, src + 12, AGN_WAVE);
+    return th;
+}
+
+// The max over the wave of four keys' p8_verdict maxima (16 values per lane),
+// as one transposed reduction: at strides 32, 16, 8 and 4 a lane keeps the
+// half of its values its lane bit selects (the key pair, the key, the
+// component pair, the component) and sends the other half to its partner, the
+// stride-2 step folds the one value left -- 8 + 4 + 2 + 1 + 1 shuffles where
+// four per-key folds take 4 x 20.  Returns the slot layout: the maximum of key
+// g = l >> 4 at DC 4 (l & 1) + 2 ((l >> 3) & 1) + ((l >> 2) & 1).
+__device__ __forceinline__ uint32_t p4_maxfold(const u32x4 (&mx)[4]) {
+    const int lane = lane_id();
+    auto xch = [](uint32_t keep, uint32_t send, int stride) {
+        const uint32_t got = (uint32_t)__shfl_xor((int)send, stride, AGN_WAVE);
+        return got > keep ? got : keep;
+    };
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0,
+               b2 = (lane & 4) != 0;
+    uint32_t v8[8], v4[4], v2[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            v8[4 * k + c] = xch(b5 ? mx[2 + k][c] : mx[k][c], b5 ? mx[k][c] : mx[2 + k][c], 32);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v4[c] = xch(b4 ? v8[4 + c] : v8[c], b4 ? v8[c] : v8[4 + c], 16);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) v2[j] = xch(b3 ? v4[2 + j] : v4[j], b3 ? v4[j] : v4[2 + j], 8);
+    const uint32_t v1 = xch(b2 ? v2[1] : v2[0], b2 ? v2[0] : v2[1], 4);
+    return xch(v1, v1, 2);
+}
+
+// Wave-uniform groups of per-key metadata as one scalar load each: the arrays
+// are aligned to their elements only.
+typedef unsigned long long u64x4 __attribute__((ext_vector_type(4)));
+typedef u64x4 u64x4_a8 __attribute__((aligned(8)));
+typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
+__device__ __forceinline__ u64x4 ldc_u64x4(const uint64_t *p) {
+    return *(const __attribute__((address_space(4))) u64x4_a8 *)p;
+}
+__device__ __forceinline__ u32x4 ldc_u32x4(const uint32_t *p) {
+    return *(const __attribute__((address_space(4))) u32x4_a4 *)p;
+}
+
 // scan_key for D = 8 with lane-CONTIGUOUS row loads ("quad rows"): load j of a
 // 64-op chunk reads bytes [1 KiB j, 1 KiB (j+1)) of the chunk's rows, so
 // every instruction covers 8 whole 128-byte lines -- the row-per-lane loads

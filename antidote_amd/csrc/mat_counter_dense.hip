@@ -52,6 +52,12 @@ inline uint32_t counter_order(uint64_t n_req, uint32_t bulk) {
     return order_or(n_req < (1ull << 20) ? 1u : bulk);
 }
 constexpr uint32_t BULK_CHUNK = 64;
+// k_counter_pack4 (four requests per block): the run per XCD -- cold cfg2 in
+// one process 4.176 ms in runs of 64, 4.217 of 32, 4.170 of 128
+// (profiles/r10/ab_q2_four.log) -- and whether the launcher takes the kernel
+// without AGN_Q2_FOUR set (4.176 against 4.752 ms there).
+constexpr uint32_t BULK_CHUNK4 = 64;
+constexpr bool Q2_FOUR_DEFAULT = true;
 
 struct DenseArgs {
     uint64_t n_req;
@@ -968,6 +974,11 @@ __device__ __forceinline__ MaskArgs mask_of(const T &x) {
     return MaskArgs{x.key_mask, x.oc_mask, x.R_mask, x.sct_mask, x.o_mask};
 }
 
+// Lane g of `old` becomes the wave-uniform v.
+__device__ __forceinline__ uint32_t put_lane(uint32_t v, int g, uint32_t old) {
+    return lane_id() == g ? v : old;
+}
+
 // k_counter_quad2's parameters past Q2Params' (its PACK form): the packed index
 // of the log (agn_log_index_pack), read from the kernarg segment where used.
 struct Q2PackParams {
@@ -1022,6 +1033,30 @@ __device__ __forceinline__ void q2_pack_ct(const Q2Pack &p, u32x4 mx, Q2Acc &s) 
     const bool hi = (lane_id() & 1) != 0;
     s.ctA = s.cnt ? p.bq.x + (uint64_t)(hi ? g2 : g0) : 0ull;
     s.ctB = s.cnt ? p.bq.y + (uint64_t)(hi ? g3 : g1) : 0ull;
+}
+
+// One request of a cold dense batch that the packed rows do not serve, read
+// from oc: its own prologue (scalar-cache hits where the caller has loaded
+// the metadata before), the quad-row scan and q2_epilogue, with every pointer
+// from the kernarg segment (Q2Params: k_counter_quad2's parameter list), so
+// the caller's straight path holds none of this in registers.  No TxIds are
+// passed: a cold read includes an op whatever its TxId (nip is all ones).
+// Same functions, same results as k_counter_quad2 without an index.
+__device__ __forceinline__ void q2_serve_oc(const DenseArgs &a, uint64_t i) {
+    const MaskArgs mk{};
+    const auto &p = kparams<Q2Params>();
+    const Q2Key k = q2_prologue<false, false>(a, mk, i, p.keys, p.key_off, p.key_len, p.key_type,
+                                              p.key_id0, p.R, p.sct, p.sct_ignore, p.req_txid);
+    Q2Acc s;
+    s.ctA = k.eA;
+    s.ctB = k.eB;
+    if (a.n_entries != 0 && !k.corrupt)
+        scan_key_q8<false, true, false, false>(p.oc, p.eff, nullptr, 0ull, k.off, k.n, a.n_entries,
+                                               k.rA, k.rB, k.sA, k.sB, s.ctA, s.ctB, s.sum, s.cnt,
+                                               s.first_excl, s.first_err, k.noR);
+    const auto &pe = kparams<Q2Params>();
+    q2_epilogue<false>(k, s, a.hints, pe.op_id, pe.base_value, pe.o_value, pe.o_hole, pe.o_lastct,
+                       pe.o_count, pe.o_flags, pe.o_err, nullptr);
 }
 
 // The dense warm form runs at 6 waves per SIMD: 80 VGPRs and 2 scratch
@@ -1176,30 +1211,11 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
     }
     if constexpr (PACK) {
         // A pair the packed rows do not serve (a key longer than a chunk or not
-        // packed, an empty log) reads oc one request after the other, each from
-        // its own prologue on (scalar-cache hits) and with every pointer from
-        // the kernarg segment: kept side by side as below, the two requests'
-        // scan state costs the straight path a wave per SIMD.  No TxIds are
-        // passed: a cold read includes an op whatever its TxId (nip is all
-        // ones).  Same functions, same results as the form without an index.
+        // packed, an empty log) reads oc one request after the other
+        // (q2_serve_oc): kept side by side as below, the two requests' scan
+        // state costs the straight path a wave per SIMD.
 #pragma nounroll
-        for (uint32_t h = 0; h < (two ? 2u : 1u); ++h) {
-            const auto &p = kparams<Q2Params>();
-            const Q2Key k = q2_prologue<ANY_WARM, MSK>(a, mk, i0 + h, p.keys, p.key_off, p.key_len,
-                                                       p.key_type, p.key_id0, p.R, p.sct,
-                                                       p.sct_ignore, p.req_txid);
-            Q2Acc s;
-            s.ctA = k.eA;
-            s.ctB = k.eB;
-            if (a.n_entries != 0 && !k.corrupt)
-                scan_key_q8<false, true, false, false>(p.oc, p.eff, nullptr, 0ull, k.off, k.n,
-                                                       a.n_entries, k.rA, k.rB, k.sA, k.sB, s.ctA,
-                                                       s.ctB, s.sum, s.cnt, s.first_excl,
-                                                       s.first_err, k.noR);
-            const auto &pe = kparams<Q2Params>();
-            q2_epilogue<MSK>(k, s, a.hints, pe.op_id, pe.base_value, pe.o_value, pe.o_hole,
-                             pe.o_lastct, pe.o_count, pe.o_flags, pe.o_err, mk.o_mask);
-        }
+        for (uint32_t h = 0; h < (two ? 2u : 1u); ++h) q2_serve_oc(a, i0 + h);
         return;
     }
     if (a.n_entries != 0) {
@@ -1232,6 +1248,192 @@ __global__ __launch_bounds__(64, (ANY_WARM && !MSK) ? 6 : 1) void k_counter_quad
     if (two)
         q2_epilogue<MSK>(k1, s1, a.hints, op_id, base_value, o_value, o_hole, o_lastct, o_count, o_flags,
                          o_err, mk.o_mask);
+}
+
+// Four requests per wave over the packed index: the whole-partition cold read
+// (identity key map, req.keys == NULL), where requests 4b .. 4b+3 are keys
+// 4b .. 4b+3 and everything per key or per request is contiguous -- one scalar
+// load per metadata array, one 8-byte-per-lane load each for the four R rows
+// and the four pack_base rows, one store per result array.  The wave holds
+// eight 16-byte row loads in flight (8 KiB) where k_counter_quad2's PACK form
+// holds four, and nothing else: no warm, masked or long-key form, every
+// pointer read from the kernarg segment where it is used (Q2PackParams is
+// k_counter_quad2's parameter list).
+//
+// The straight path serves a group whose four requests exist, are packed
+// (pack_ok), fit one chunk and are not corrupt, over a non-empty log.  Per
+// (key, DC) values sit in the slot layout (counter_scan.hpp, p4_slot), so
+// the thresholds reach p8_verdict's layout by four shuffles per key, the four
+// LastOpCt rows fold as one transposed reduction (p4_maxfold: 16 shuffles;
+// four q2_pack_ct take 80 and sixteen DPP moves) and leave as one 256-byte
+// store.  Order: metadata -> the eight row loads -> per key verdict and
+// deferred effect load -> the fold, under the effects -> the effects' fold ->
+// stores (loads and stores share the VM counter: no store before the last
+// use of a load).  Every other group -- and the last one of a batch that is
+// no multiple of four, which reads nothing past request n_req - 1 -- runs its
+// requests one after the other through oc (q2_serve_oc).  Same results as
+// k_counter_quad2.
+__global__ __launch_bounds__(64) void k_counter_pack4(Q2PackParams) {
+    const DenseArgs a = dense_of(kparams<Q2Params>().a);
+    const uint32_t blk = block_order(a.xcd, blockIdx.x, gridDim.x);
+    const uint64_t i0 = uniform_u64((uint64_t)blk * 4u);
+    if (i0 >= a.n_req) return;
+    const int lane = lane_id();
+    if (i0 + 3u < a.n_req) {
+        // One scalar round trip, every address a function of the block alone;
+        // absent arrays read an in-bounds dummy (key_meta's convention).  With
+        // key_len the segment ends need no key_off[4b + 4] (the array may end
+        // at n_keys entries), without it the fifth offset exists: 4b + 4 <= n_keys.
+        const auto &pm = kparams<Q2Params>();
+        const uint64_t *const key_off = pm.key_off, *const key_len = pm.key_len;
+        const uint32_t *const key_id0 = pm.key_id0;
+        const uint8_t *const key_type = pm.key_type;
+        const uint64_t *const R = pm.R;
+        // (one kernarg read for both views: Q2PackParams extends Q2Params' list)
+        const auto &pq = *(const __attribute__((address_space(4))) Q2PackParams *)&pm;
+        const uint64_t *const pbase = pq.base;
+        const uint8_t *const pok = pq.ok;
+        const int64_t *const bvp = pm.base_value;
+        const u64x4 offv = ldc_u64x4(key_off + i0);
+        const u64x4 lenv = ldc_u64x4(key_len ? key_len + i0 : key_off + i0);
+        const u32x4 idv = ldc_u32x4(key_id0 ? key_id0 + i0
+                                            : reinterpret_cast<const uint32_t *>(key_off + i0));
+        const uint8_t *const ktp = key_type ? key_type : reinterpret_cast<const uint8_t *>(key_off);
+        uint64_t off[5], ln[4];
+        uint32_t id0[4];
+        off[4] = uniform_u64(ldc(key_len ? key_off + i0 : key_off + i0 + 4u));
+        uint32_t ktw = __builtin_amdgcn_readfirstlane(ldc(reinterpret_cast<const uint32_t *>(ktp) + (i0 >> 2)));
+        uint32_t okw = __builtin_amdgcn_readfirstlane(ldc(reinterpret_cast<const uint32_t *>(pok) + (i0 >> 2)));
+        // R and pack_base of the four requests, in the slot layout: 256
+        // contiguous bytes each, needing only the block index
+        const uint64_t slot = i0 * 8u + (uint64_t)p4_slot(lane);
+        const uint64_t rv = R[slot], bv = pbase[slot];
+        // base_value of request 4b + (lane & 3): lanes 0-3 compute the results
+        const uint64_t bvl = *(bvp ? reinterpret_cast<const uint64_t *>(bvp) + (i0 + (uint64_t)(lane & 3))
+                                   : R + slot);
+        const uint64_t reqbase = bvp ? bvl : 0ull;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            off[g] = uniform_u64(offv[g]);
+            ln[g] = uniform_u64(lenv[g]);
+            id0[g] = (uint32_t)__builtin_amdgcn_readfirstlane(idv[g]);
+        }
+        // every load above is issued before the first use of any (q2_pin): left
+        // alone, a load used under one condition only sinks behind the wait
+        // for the others
+        asm volatile("" : "+s"(off[0]), "+s"(off[1]), "+s"(off[2]), "+s"(off[3]), "+s"(off[4]),
+                          "+s"(ln[0]), "+s"(ln[1]), "+s"(ln[2]), "+s"(ln[3]), "+s"(id0[0]),
+                          "+s"(id0[1]), "+s"(id0[2]), "+s"(id0[3]), "+s"(ktw), "+s"(okw));
+        const bool has_len = key_len != nullptr, has_id0 = key_id0 != nullptr;
+        const uint32_t want = key_type != nullptr ? (a.req_type & 0xffu) * 0x01010101u : ktw;
+        uint32_t n[4];
+        // served: all packed, a log to read; each key within a chunk and of the
+        // request's type (an empty key's type is not looked at)
+        uint32_t bad = (okw ^ 0x01010101u) | (a.n_entries == 0 ? 1u : 0u);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const uint64_t n64 = has_len ? ln[g] : off[g + 1] - off[g];
+            n[g] = (uint32_t)n64;
+            id0[g] = has_id0 ? id0[g] : AGN_ID0_NONE;
+            const uint32_t kdiff = ((ktw ^ want) >> (8 * g)) & 0xffu;
+            bad |= (n64 > (uint64_t)AGN_WAVE ? 1u : 0u) | (n64 != 0 ? kdiff : 0u);
+        }
+        if (bad == 0u) {
+            // (read here: held over the check, the pointer costs the SGPR file a spill)
+            const uint32_t *const rows = kparams<Q2PackParams>().rows;
+            P8Rows c[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) c[g] = p8_load_rows<true>(rows, off[g], 0, a.n_entries);
+            const int64_t *const l_eff = kparams<Q2Params>().eff;
+            // all eight row loads are in flight before the first verdict
+            __builtin_amdgcn_sched_barrier(0);
+            // thresholds min(R - base, 2^32 - 1); noR of key g: its 16 lanes' bits
+            const uint64_t below = ballot(rv < bv);
+            const uint64_t dl = rv - bv;
+            const uint32_t t = (dl >> 32) ? 0xFFFFFFFFu : (uint32_t)dl;
+            // Request g's scalars move to lane g as they are made, where
+            // the results are computed once for the four: held as
+            // scalars to the stores, four requests' state does not fit the
+            // SGPR file.  first_excl and first_err are positions < 64 or -1.
+            uint32_t v_off_lo = 0, v_off_hi = 0, v_n = 0, v_id0 = 0, v_cnt = 0, v_fx = 0, v_fe = 0,
+                     v_sum_lo = 0, v_sum_hi = 0;
+            uint32_t cg = 0;  // the count of key lane >> 4, the slot layout's key
+            const int kg = lane >> 4;
+            u32x4 mx[4];
+            uint64_t in[4];
+            int64_t ev[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const u32x4 th = p4_thr(t, g);
+                const bool noR = ((below >> (16 * g)) & 0xFFFFull) != 0ull;
+                uint32_t cnt = 0;
+                int64_t fx = -1;
+                mx[g] = u32x4{0u, 0u, 0u, 0u};
+                in[g] = p8_verdict(c[g], 0, (uint64_t)n[g], th, noR, mx[g], cnt, fx);
+                ev[g] = q8_load_eff(l_eff, off[g], 0, in[g],
+                                    reinterpret_cast<const int64_t *>(R + (i0 + (uint64_t)g) * 8u));
+                __builtin_amdgcn_sched_barrier(0);  // key g's effects go out before key g + 1's verdict
+                cg = kg == g ? cnt : cg;
+                v_cnt = put_lane(cnt, g, v_cnt);
+                v_fx = put_lane((uint32_t)fx, g, v_fx);
+                v_off_lo = put_lane((uint32_t)off[g], g, v_off_lo);
+                v_off_hi = put_lane((uint32_t)(off[g] >> 32), g, v_off_hi);
+                v_n = put_lane(n[g], g, v_n);
+                v_id0 = put_lane(id0[g], g, v_id0);
+            }
+            __builtin_amdgcn_sched_barrier(0);  // the four effect loads are in flight from here
+            // The pointers the results need are read here, under the effects
+            // (k_counter_quad2).  Where the log has no id index, lanes 0-3 load
+            // the op id that defines their request's NewLastOp -- one load; the
+            // other lanes read an address the wave has fetched.
+            const auto &pr = kparams<Q2Params>();
+            const uint32_t *const l_op_id = pr.op_id;
+            int64_t *const l_value = pr.o_value, *const l_hole = pr.o_hole;
+            uint64_t *const l_lastct = pr.o_lastct;
+            uint32_t *const l_count = pr.o_count, *const l_flags = pr.o_flags, *const l_err = pr.o_err;
+            const uint64_t v_off = ((uint64_t)v_off_hi << 32) | v_off_lo;
+            const int32_t fx = (int32_t)v_fx;
+            const uint32_t pos = fx >= 0 ? (uint32_t)fx : v_n - 1u;
+            const bool need = lane < 4 && v_id0 == AGN_ID0_NONE && v_n != 0u;
+            const uint32_t *const ip = need ? l_op_id + (v_off + (uint64_t)pos)
+                                            : reinterpret_cast<const uint32_t *>(R + slot);
+            const uint32_t opid = *ip;
+            // LastOpCt = base + max delta where the key included an op, else 0 (cold)
+            const uint32_t md = p4_maxfold(mx);
+            const uint64_t ct = cg ? bv + (uint64_t)md : 0ull;
+            __builtin_amdgcn_sched_barrier(0);  // the wait for the effects: after the fold
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                int64_t sum = 0, fe = -1;
+                q8_fold_eff(in[g], ev[g], 0, sum, fe);
+                const uint64_t total = (uint64_t)wave_sum_dpp(sum);
+                v_fe = put_lane((uint32_t)fe, g, v_fe);
+                v_sum_lo = put_lane((uint32_t)total, g, v_sum_lo);
+                v_sum_hi = put_lane((uint32_t)(total >> 32), g, v_sum_hi);
+            }
+            __builtin_amdgcn_sched_barrier(0);  // and no store before it
+            // lane g < 4: request g's result, as q2_result's of a cold read
+            const uint64_t idh = v_id0 != AGN_ID0_NONE ? (uint64_t)v_id0 + (uint64_t)pos : (uint64_t)opid;
+            const int64_t hid = v_n ? (int64_t)idh : 0;  // get_first_id of no ops: 0
+            const int32_t fe = (int32_t)v_fe;
+            uint32_t fl = v_cnt ? AGN_F_NEWSS : AGN_F_CT_IGNORE;
+            fl |= fe >= 0 ? AGN_F_ERR_UNEXPECTED : 0u;
+            if ((lane & 2) == 0) l_lastct[slot] = ct;  // the four rows: 256 contiguous bytes
+            if (lane < 4) {  // one store per array
+                const uint64_t i = i0 + (uint64_t)lane;
+                l_value[i] = (int64_t)(reqbase + (((uint64_t)v_sum_hi << 32) | v_sum_lo));
+                l_hole[i] = fx >= 0 ? hid - 1 : hid;
+                l_count[i] = v_cnt;
+                l_err[i] = fe >= 0 ? (uint32_t)(v_off + (uint64_t)fe) : 0xffffffffu;
+                l_flags[i] = fl;
+            }
+            return;
+        }
+    }
+    const uint64_t left = a.n_req - i0;
+    const uint32_t m = left < 4u ? (uint32_t)left : 4u;
+#pragma nounroll
+    for (uint32_t h = 0; h < m; ++h) q2_serve_oc(a, i0 + h);
 }
 
 // ROWS_QUAD with the first chunk EARLY (D = 8, one request per wave; the
@@ -1481,7 +1683,24 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
     const char *pv = AGN_KNOB("AGN_Q2_PACK");
     const bool pack = dflt && q2e && q2s && log.n_entries != 0 && !(pv && pv[0] == '0') &&
                       pack_lookup(log, &pk);
-    if (pack) {
+    // AGN_Q2_FOUR = 0|1 (A/B knob): the packed read of a whole partition
+    // (identity key map) runs four requests per wave, k_counter_pack4.
+    // A log of more than 64 entries per key on average keeps two per wave: its
+    // groups mostly hold a key longer than a chunk and would run four
+    // requests one after the other (3M keys x 200 ops: 8.37 against 8.31 ms).
+    const char *fv = AGN_KNOB("AGN_Q2_FOUR");
+    const bool four = pack && !req.keys && log.n_entries / 64u <= log.n_keys &&
+                      ((fv && (fv[0] == '0' || fv[0] == '1')) ? fv[0] == '1' : Q2_FOUR_DEFAULT);
+    if (four) {
+        a.xcd = counter_order(req.n_req, BULK_CHUNK4);
+        const Q2PackParams p{a, mk,
+                             {req.keys, log.key_off, log.key_len, log.key_type, id0_index(log),
+                              log.oc, log.op_id, log.eff, log.txid, req.R, req.sct, req.sct_ignore,
+                              req.txid, req.base_value, out.value, out.hole, out.lastct, out.count,
+                              out.flags, out.err_pos},
+                             pk.rows, pk.base, pk.ok};
+        hipLaunchKernelGGL(k_counter_pack4, dim3((unsigned)((req.n_req + 3) / 4)), dim3(64), 0, st, p);
+    } else if (pack) {
         AGN_Q2L_(false, false, true, true, true);
     } else if (req.sct) {
         if (msk) AGN_Q2L(true, true);
