@@ -149,6 +149,7 @@ PROTOTYPES = {
     "agn_log_index_ids": (C.c_int, [P, C.POINTER(AgnLog), P, P]),
     "agn_log_index_masks": (C.c_int, [P, C.POINTER(AgnLog), P, P]),
     "agn_log_index_pack": (C.c_int, [P, C.POINTER(AgnLog), P, P, P, C.POINTER(C.c_uint64), P]),
+    "agn_log_index_pack16": (C.c_int, [P, C.POINTER(AgnLog), P, P, C.POINTER(C.c_uint64), P]),
     "agn_tune": (C.c_int, [P, C.POINTER(AgnLog), C.POINTER(AgnRead), C.POINTER(AgnResult), P,
                            C.c_int, C.POINTER(C.c_int), P]),
     "agn_select_base": (C.c_int, [P, C.c_uint32, C.c_uint64, P, P, P, P, P, P, P, P]),
@@ -226,8 +227,16 @@ ORACLE_PROTOTYPES = {
 }
 
 
+# Additions to ABI v7 (no struct changed, the version number stayed): a library
+# built before them still loads -- an A/B against an earlier build of the same
+# ABI through AGN_LIB -- and calling a missing one raises AttributeError.
+ADDITIVE = frozenset({"agn_log_index_pack16"})
+
+
 def bind(lib, protos):
     for name, (res, args) in protos.items():
+        if name in ADDITIVE and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

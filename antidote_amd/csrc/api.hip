@@ -191,6 +191,7 @@ struct PackEnt {
     uint64_t n_entries, n_keys, seq;
     PackIdx idx;
     bool owned;  // agn_gen_dev's buffers: freed with the entry
+    bool owned16;  // and the narrow tier's (idx.rows16, idx.narrow)
 };
 constexpr int kPackIdx = 16;
 std::mutex g_pk_mu;
@@ -198,8 +199,21 @@ PackEnt g_pk[kPackIdx] = {};
 uint64_t g_pk_seq = 0;
 std::atomic<int> g_pk_live{0};
 
+// The entry's narrow tier alone (agn_log_index_pack16): the u32 index stays.
+void pack_drop16_locked(PackEnt &e) {
+    if (e.owned16) {
+        (void)hipFree((void *)e.idx.rows16);
+        (void)hipFree((void *)e.idx.narrow);
+    }
+    e.idx.rows16 = nullptr;
+    e.idx.narrow = nullptr;
+    e.idx.n_wide = 0;
+    e.owned16 = false;
+}
+
 void pack_drop_locked(PackEnt &e) {
     if (!e.ctx) return;
+    pack_drop16_locked(e);
     if (e.owned) {
         (void)hipFree((void *)e.idx.rows);
         (void)hipFree((void *)e.idx.base);
@@ -236,8 +250,33 @@ void pack_register(agn_ctx *ctx, const agn_log &log, const PackIdx &idx, bool ow
             if (e.seq < slot->seq) slot = &e;
     }
     pack_drop_locked(*slot);
-    *slot = {ctx, log.oc, log.key_off, log.n_entries, log.n_keys, ++g_pk_seq, idx, owned};
+    *slot = {ctx, log.oc, log.key_off, log.n_entries, log.n_keys, ++g_pk_seq, idx, owned, false};
     g_pk_live.fetch_add(1, std::memory_order_release);
+}
+
+// Drop the narrow tier of the log's entry, if any.
+void pack_unregister16(const agn_log &log) {
+    if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (pack_match(e, log)) pack_drop16_locked(e);
+}
+
+// Attach a narrow tier to the log's entry (replacing one); false when the log
+// has no entry (dropped or evicted since the caller looked it up).
+bool pack_register16(const agn_log &log, const uint16_t *rows16, const uint8_t *narrow,
+                     uint64_t n_wide, bool owned) {
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (pack_match(e, log)) {
+            pack_drop16_locked(e);
+            e.idx.rows16 = rows16;
+            e.idx.narrow = narrow;
+            e.idx.n_wide = n_wide;
+            e.owned16 = owned;
+            return true;
+        }
+    return false;
 }
 
 // agn_close: the context's entries.
@@ -252,10 +291,13 @@ void pack_clear(agn_ctx *ctx) {
 void pack_forget(const void *p) {
     if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
     std::lock_guard<std::mutex> g(g_pk_mu);
-    for (auto &e : g_pk)
-        if (e.ctx && (p == e.oc || p == e.key_off || p == e.idx.rows || p == e.idx.base ||
-                      p == e.idx.ok))
+    for (auto &e : g_pk) {
+        if (!e.ctx) continue;
+        if (p == e.oc || p == e.key_off || p == e.idx.rows || p == e.idx.base || p == e.idx.ok)
             pack_drop_locked(e);
+        else if (e.idx.rows16 && (p == e.idx.rows16 || p == e.idx.narrow))
+            pack_drop16_locked(e);  // the narrow tier alone: the u32 index stays
+    }
 }
 }  // namespace
 
@@ -545,6 +587,35 @@ int agn_log_index_pack(agn_ctx *ctx, const agn_log *log, uint32_t *rows, uint64_
     rc = launch_index_pack(*log, rows, base, ok, n_unpacked, (hipStream_t)stream);
     if (rc) return rc;
     pack_register(ctx, *log, PackIdx{rows, base, ok}, false);
+    return AGN_OK;
+}
+
+int agn_log_index_pack16(agn_ctx *ctx, const agn_log *log, uint16_t *rows16, uint8_t *narrow,
+                         uint64_t *n_wide, void *stream) {
+    if (!log) return fail(AGN_EINVAL, "index_pack16: null log");
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if (n_wide) *n_wide = 0;
+    if (!rows16) {  // drop the narrow tier; the u32 index stays registered
+        pack_unregister16(*log);
+        return AGN_OK;
+    }
+    if (log->crdt_type != AGN_COUNTER_PN || log->n_dcs != 8 || log->oc_mask)
+        return fail(AGN_ENOTSUP, "index_pack16: counter_pn logs with 8 dense DCs only");
+    if (!narrow) return fail(AGN_EINVAL, "index_pack16: narrow required");
+    // the kernels read rows16 as 16-byte units and narrow as aligned dwords
+    if (((uintptr_t)rows16 & 15u) || misaligned4(narrow))
+        return fail(AGN_EINVAL, "index_pack16: rows16 16-byte, narrow 4-byte aligned");
+    PackIdx pk{};
+    if (!pack_lookup(*log, &pk))
+        return fail(AGN_EINVAL, "index_pack16: no packed index registered for the log "
+                                "(agn_log_index_pack first)");
+    uint64_t wide = 0;
+    rc = launch_index_pack16(*log, pk.rows, pk.ok, rows16, narrow, &wide, (hipStream_t)stream);
+    if (rc) return rc;
+    if (n_wide) *n_wide = wide;
+    if (!pack_register16(*log, rows16, narrow, wide, false))
+        return fail(AGN_EINVAL, "index_pack16: the log's packed index was dropped meanwhile");
     return AGN_OK;
 }
 
@@ -1380,6 +1451,22 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
             launch_index_pack(*log, (uint32_t *)pr, (uint64_t *)pb, (uint8_t *)po, nullptr, s) ==
                 AGN_OK) {
             pack_register(ctx, *log, PackIdx{(uint32_t *)pr, (uint64_t *)pb, (uint8_t *)po}, true);
+            // and its narrow tier (agn_log_index_pack16), where it can be
+            // allocated: without it the log keeps the u32 index alone
+            void *p16 = nullptr, *pn = nullptr;
+            uint64_t wide = 0;
+            const bool tier =
+                hipMalloc(&p16, E * 8 * sizeof(uint16_t)) == hipSuccess &&
+                hipMalloc(&pn, (K + 7) / 8 * 8) == hipSuccess &&
+                launch_index_pack16(*log, (const uint32_t *)pr, (const uint8_t *)po, (uint16_t *)p16,
+                                    (uint8_t *)pn, &wide, s) == AGN_OK &&
+                pack_register16(*log, (const uint16_t *)p16, (const uint8_t *)pn, wide, true);
+            if (!tier) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(s);
+                if (p16) (void)hipFree(p16);
+                if (pn) (void)hipFree(pn);
+            }
         } else {
             (void)hipGetLastError();
             (void)hipStreamSynchronize(s);

@@ -310,14 +310,24 @@ int launch_index_ids(const agn_log &log, uint32_t *out, hipStream_t st);
 int launch_index_masks(const agn_log &log, uint64_t *out, uint64_t *mixed, hipStream_t st);
 // The packed index of a log (agn_log_index_pack): u32 deltas [n_entries][8],
 // column bases [n_keys][8], packed flag [n_keys].
+// Its narrow tier (agn_log_index_pack16; absent: rows16 == nullptr): u16
+// deltas [n_entries][8] of the keys whose columns span at most 2^16 - 1,
+// narrow flag [n_keys], and the count of keys with narrow == 0.
 struct PackIdx {
     const uint32_t *rows;
     const uint64_t *base;
     const uint8_t *ok;
+    const uint16_t *rows16;
+    const uint8_t *narrow;
+    uint64_t n_wide;
 };
 // n_unpacked (optional): the count of unpacked keys, read back (blocks).
 int launch_index_pack(const agn_log &log, uint32_t *rows, uint64_t *base, uint8_t *ok,
                       uint64_t *n_unpacked, hipStream_t st);
+// The narrow tier from the u32 index; *n_wide: the keys with narrow == 0,
+// read back (always: the call blocks).
+int launch_index_pack16(const agn_log &log, const uint32_t *rows, const uint8_t *ok,
+                        uint16_t *rows16, uint8_t *narrow, uint64_t *n_wide, hipStream_t st);
 // The index registered for this log (api.hip; the launchers carry no
 // context, so the table is the process's, each entry owned by a context);
 // *out is written only when one is found.

@@ -568,6 +568,112 @@ __device__ __forceinline__ uint32_t p4_maxfold(const u32x4 (&mx)[4]) {
     return xch(v1, v1, 2);
 }
 
+// ---- eight narrow keys per wave (k_counter_pack8) --------------------------
+// The narrow tier's rows (agn_log_index_pack16): u16 deltas, 16 bytes per op,
+// so lane l holds all eight DCs of op l of a key -- dword j its DCs 2j (low
+// half) and 2j + 1 -- and a key's verdict is one ballot.  The wave's
+// per-(key, DC) values live one per lane: lane l holds key l >> 3, DC l & 7.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+// The maxima of the two u16 halves, each on its own.
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
+    const u16x2 m = __builtin_elementwise_max(__builtin_bit_cast(u16x2, a),
+                                              __builtin_bit_cast(u16x2, b));
+    return __builtin_bit_cast(uint32_t, m);
+}
+
+__device__ __forceinline__ uint64_t n8_readlane_u64(uint64_t v, int l) {
+    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, l);
+    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// The 16-byte unit of entry off + lane, clamped at the log's end (the caller
+// masks the lanes past the key's length).
+template <bool NT>
+__device__ __forceinline__ u32x4 n8_load_rows(const uint16_t *__restrict__ rows16, uint64_t off,
+                                              uint64_t n_entries) {
+    uint64_t e = off + (uint64_t)lane_id();
+    e = e < n_entries - 1u ? e : n_entries - 1u;
+    return ld<NT>(reinterpret_cast<const u32x4 *>(rows16) + e);
+}
+
+// The thresholds min(R - base, 2^16 - 1) of the per-(key, DC) layout, two per
+// dword: an even lane 8g + 2j gets DCs 2j (low half) and 2j + 1 of key g, the
+// halves of row dword j.
+__device__ __forceinline__ uint32_t n8_thr_pack(uint32_t t) {
+    const uint32_t nx = __builtin_amdgcn_update_dpp(0u, t, 0xF5, 0xF, 0xF, false);  // quad_perm 1,1,3,3
+    return t | (nx << 16);
+}
+
+// Nonzero iff this lane's op is excluded by some column: a u16 delta above its
+// threshold (th[j]: the thresholds of DCs 2j, 2j + 1, wave-uniform).
+// max(d, th) != th per half, so neither half of a dword reaches into the
+// other; no short circuit (a branch between the row loads' waits).
+__device__ __forceinline__ uint32_t n8_excl(const u32x4 &d, uint32_t th0, uint32_t th1,
+                                            uint32_t th2, uint32_t th3) {
+    return (pk_max_u16(d.x, th0) ^ th0) | (pk_max_u16(d.y, th1) ^ th1) |
+           (pk_max_u16(d.z, th2) ^ th2) | (pk_max_u16(d.w, th3) ^ th3);
+}
+
+// q8_load_eff for a lane that knows its own verdict.
+__device__ __forceinline__ int64_t n8_load_eff(const int64_t *__restrict__ eff, uint64_t off,
+                                               bool mine, const int64_t *__restrict__ dummy) {
+    const int64_t *p = mine ? eff + (off + (uint64_t)lane_id()) : dummy;
+    return *p;
+}
+
+// The max over the wave (lane = op) of eight keys' included deltas (4 dwords
+// of 2 halves per key and lane), as one transposed reduction: at strides 32,
+// 16 and 8 a lane keeps the keys its lane bit selects and sends the others to
+// its partner, at strides 4 and 2 the dwords, at stride 1 one half-word --
+// 16 + 8 + 4 + 2 + 1 + 1 exchanges.  Returns the per-(key, DC) layout: lane l
+// holds the maximum of key l >> 3 at DC l & 7.
+__device__ __forceinline__ uint32_t n8_maxfold(const u32x4 (&mx)[8]) {
+    const int lane = lane_id();
+    auto xch = [](uint32_t keep, uint32_t send, int stride) {
+        return pk_max_u16((uint32_t)__shfl_xor((int)send, stride, AGN_WAVE), keep);
+    };
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0,
+               b2 = (lane & 4) != 0, b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
+    uint32_t v16[16], v8[8], v4[4], v2[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            v16[4 * k + c] = xch(b5 ? mx[4 + k][c] : mx[k][c], b5 ? mx[k][c] : mx[4 + k][c], 32);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v8[c] = xch(b4 ? v16[8 + c] : v16[c], b4 ? v16[c] : v16[8 + c], 16);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v4[c] = xch(b3 ? v8[4 + c] : v8[c], b3 ? v8[c] : v8[4 + c], 8);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) v2[j] = xch(b2 ? v4[2 + j] : v4[j], b2 ? v4[j] : v4[2 + j], 4);
+    const uint32_t v1 = xch(b1 ? v2[1] : v2[0], b1 ? v2[0] : v2[1], 2);
+    const uint32_t m = xch(v1, v1, 1);
+    return b0 ? m >> 16 : m & 0xFFFFu;
+}
+
+// The i64 sums over the wave of eight keys' per-lane terms, transposed the
+// same way: strides 32, 16 and 8 halve the keys, three DPP steps then sum each
+// aligned group of eight lanes.  Lane l holds the sum of key l >> 3.
+__device__ __forceinline__ uint64_t n8_sumfold(const uint64_t (&s)[8]) {
+    const int lane = lane_id();
+    auto xch = [](uint64_t keep, uint64_t send, int stride) {
+        return keep + shfl_xor_u64(send, stride);
+    };
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
+    uint64_t v4[4], v2[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v4[k] = xch(b5 ? s[4 + k] : s[k], b5 ? s[k] : s[4 + k], 32);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) v2[k] = xch(b4 ? v4[2 + k] : v4[k], b4 ? v4[k] : v4[2 + k], 16);
+    uint64_t v = xch(b3 ? v2[1] : v2[0], b3 ? v2[0] : v2[1], 8);
+    v += dpp_u64(v, 0);
+    v += dpp_u64(v, 1);
+    v += dpp_u64(v, 2);
+    return v;
+}
+
 // Wave-uniform groups of per-key metadata as one scalar load each: the arrays
 // are aligned to their elements only.
 typedef unsigned long long u64x4 __attribute__((ext_vector_type(4)));

@@ -58,6 +58,16 @@ constexpr uint32_t BULK_CHUNK = 64;
 // without AGN_Q2_FOUR set (4.176 against 4.752 ms there).
 constexpr uint32_t BULK_CHUNK4 = 64;
 constexpr bool Q2_FOUR_DEFAULT = true;
+// k_counter_pack8 (eight requests per block over the narrow tier): the run per
+// XCD -- cold cfg2 in one process 2.549 ms in runs of 64, 2.615 of 32, 2.547 of
+// 128 (profiles/r11/ab_q2_narrow.log) -- and the launcher's bound on the log's
+// wide keys: at most one key in NARROW_WIDE_DIV may lack the narrow form (a
+// group holding one runs its eight requests one after the other through oc).
+// At the bound, 1M keys x 64 ops with one key in 1024 wide, the kernel ran
+// 0.331 against 0.469 ms for k_counter_pack4 (1.42x; one in 256: 1.32x;
+// profiles/r11/ab_narrow_bound.log), so the bound stands as estimated.
+constexpr uint32_t BULK_CHUNK8 = 64;
+constexpr uint64_t NARROW_WIDE_DIV = 1024;
 
 struct DenseArgs {
     uint64_t n_req;
@@ -1436,6 +1446,198 @@ __global__ __launch_bounds__(64) void k_counter_pack4(Q2PackParams) {
     for (uint32_t h = 0; h < m; ++h) q2_serve_oc(a, i0 + h);
 }
 
+// k_counter_pack4's parameters and the narrow tier of the packed index
+// (agn_log_index_pack16).
+struct Q2Pack8Params {
+    DenseArgs a;
+    MaskArgs mk;
+    const void *args[20];  // keys .. o_err
+    const uint32_t *rows;
+    const uint64_t *base;
+    const uint8_t *ok;
+    const uint16_t *rows16;
+    const uint8_t *narrow;
+};
+static_assert(offsetof(Q2Pack8Params, rows) == offsetof(Q2PackParams, rows) &&
+                  offsetof(Q2Pack8Params, base) == offsetof(Q2PackParams, base),
+              "Q2Pack8Params extends Q2PackParams");
+
+// Eight requests per wave over the narrow tier: k_counter_pack4's launch
+// (cold, dense, the identity key map) where the log's keys are narrow -- u16
+// deltas, 16 bytes per op, a 64-op key 1 KiB: lane l loads the whole row of
+// op l, so eight keys are the same eight 16-byte loads per lane (8 KiB in
+// flight per wave) that four keys are over the u32 rows.
+//
+// The straight path serves a group whose eight requests exist, are narrow
+// (both dwords of `narrow`), fit one chunk and are not corrupt, over a
+// non-empty log.  The per-key metadata is loaded and the results are computed
+// as vectors in lanes 0-7 (eight requests' scalars do not fit the SGPR file);
+// a key's offset and length are lane reads where a wave-uniform value is
+// needed.  R, pack_base, the thresholds and LastOpCt are one value per lane
+// (key l >> 3, DC l & 7): 512 contiguous bytes per array.  Order: metadata ->
+// the eight row loads -> per key verdict (one ballot: a lane holds every DC of
+// its op) and deferred effect load, the row registers keeping the included
+// op's deltas -> one transposed max fold and the op-id load, under the
+// effects -> the effects' transposed sum -> stores.  Every other group -- and
+// the last one of a batch that is no multiple of eight, which reads nothing
+// past request n_req - 1 -- runs its requests one after the other through oc
+// (q2_serve_oc).  Same results as k_counter_quad2.
+__global__ __launch_bounds__(64) void k_counter_pack8(Q2Pack8Params) {
+    const DenseArgs a = dense_of(kparams<Q2Params>().a);
+    const uint32_t blk = block_order(a.xcd, blockIdx.x, gridDim.x);
+    const uint64_t i0 = uniform_u64((uint64_t)blk * 8u);
+    if (i0 >= a.n_req) return;
+    const int lane = lane_id();
+    if (i0 + 7u < a.n_req) {
+        // One round trip, every address a function of the block and the lane
+        // alone; absent arrays read an in-bounds dummy (key_meta's
+        // convention).  Lanes 0-7 hold requests 8b .. 8b+7, lane 8 the ninth
+        // offset, which exists without key_len: 8b + 8 <= n_keys.
+        const auto &pm = kparams<Q2Params>();
+        const uint64_t *const key_off = pm.key_off, *const key_len = pm.key_len;
+        const uint32_t *const key_id0 = pm.key_id0;
+        const uint8_t *const key_type = pm.key_type;
+        const uint64_t *const R = pm.R;
+        const int64_t *const bvp = pm.base_value;
+        const auto &pq = *(const __attribute__((address_space(4))) Q2Pack8Params *)&pm;
+        const uint64_t *const pbase = pq.base;
+        const uint8_t *const pnar = pq.narrow;
+        const bool has_len = key_len != nullptr, has_id0 = key_id0 != nullptr;
+        const uint32_t m8 = (uint32_t)lane & 7u;
+        const uint64_t *const op = key_off + i0 + (uint64_t)((!has_len && lane >= 8) ? 8u : m8);
+        const uint64_t v_off = *op;
+        const uint64_t v_lr = *(has_len ? key_len + i0 + m8 : op);
+        const uint32_t v_ir = *(has_id0 ? key_id0 + i0 + m8 : reinterpret_cast<const uint32_t *>(op));
+        const uint8_t *const ktp = key_type ? key_type : reinterpret_cast<const uint8_t *>(key_off);
+        uint32_t ktw0 = __builtin_amdgcn_readfirstlane(ldc(reinterpret_cast<const uint32_t *>(ktp) + (i0 >> 2)));
+        uint32_t ktw1 = __builtin_amdgcn_readfirstlane(ldc(reinterpret_cast<const uint32_t *>(ktp) + (i0 >> 2) + 1u));
+        uint32_t nw0 = __builtin_amdgcn_readfirstlane(ldc(reinterpret_cast<const uint32_t *>(pnar) + (i0 >> 2)));
+        uint32_t nw1 = __builtin_amdgcn_readfirstlane(ldc(reinterpret_cast<const uint32_t *>(pnar) + (i0 >> 2) + 1u));
+        // R and pack_base of the eight requests: 512 contiguous bytes each
+        const uint64_t slot = i0 * 8u + (uint64_t)lane;
+        const uint64_t rv = R[slot], bv = pbase[slot];
+        const uint64_t bvl = *(bvp ? reinterpret_cast<const uint64_t *>(bvp) + (i0 + m8) : R + slot);
+        const uint64_t reqbase = bvp ? bvl : 0ull;
+        // the next lane's offset (row_shl:1; lanes 0-7 sit in one row)
+        const uint64_t v_nx =
+            ((uint64_t)__builtin_amdgcn_update_dpp(0u, (uint32_t)(v_off >> 32), 0x101, 0xF, 0xF, false) << 32) |
+            __builtin_amdgcn_update_dpp(0u, (uint32_t)v_off, 0x101, 0xF, 0xF, false);
+        const uint64_t v_n64 = has_len ? v_lr : v_nx - v_off;
+        const uint32_t v_n = (uint32_t)v_n64;
+        const uint32_t v_id0 = has_id0 ? v_ir : AGN_ID0_NONE;
+        // served: all narrow, a log to read; each key within a chunk and of the
+        // request's type (an empty key's type is not looked at)
+        const uint32_t kt = (((lane & 4) ? ktw1 : ktw0) >> (8u * ((uint32_t)lane & 3u))) & 0xffu;
+        const uint32_t want = key_type != nullptr ? (a.req_type & 0xffu) : kt;
+        const bool lbad = lane < 8 && (v_n64 > (uint64_t)AGN_WAVE || (v_n64 != 0 && kt != want));
+        const bool bad = ballot(lbad) != 0ull || nw0 != 0x01010101u || nw1 != 0x01010101u ||
+                         a.n_entries == 0;
+        if (!bad) {
+            const uint16_t *const rows16 = kparams<Q2Pack8Params>().rows16;
+            u32x4 c[8];
+#pragma unroll
+            for (int g = 0; g < 8; ++g)
+                c[g] = n8_load_rows<true>(rows16, n8_readlane_u64(v_off, g), a.n_entries);
+            const int64_t *const l_eff = kparams<Q2Params>().eff;
+            // all eight row loads are in flight before the first verdict
+            __builtin_amdgcn_sched_barrier(0);
+            // thresholds min(R - base, 2^16 - 1); noR of key g: its 8 lanes' bits
+            const uint64_t below = ballot(rv < bv);
+            const uint64_t dl = rv - bv;
+            const uint32_t tp = n8_thr_pack(dl > 0xFFFFull ? 0xFFFFu : (uint32_t)dl);
+            // first_excl and first_err are positions < 64 or -1; request g's go
+            // to lane g, the lanes' own verdicts to bit g of v_inc
+            uint32_t v_cnt = 0, v_fx = 0, v_fe = 0, v_inc = 0;
+            uint32_t cg = 0;  // the count of key lane >> 3, this lane's key
+            const int kg = lane >> 3;
+            int64_t ev[8];
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const uint32_t th0 = __builtin_amdgcn_readlane(tp, 8 * g);
+                const uint32_t th1 = __builtin_amdgcn_readlane(tp, 8 * g + 2);
+                const uint32_t th2 = __builtin_amdgcn_readlane(tp, 8 * g + 4);
+                const uint32_t th3 = __builtin_amdgcn_readlane(tp, 8 * g + 6);
+                const uint32_t noR = (uint32_t)(below >> (8 * g)) & 0xFFu;
+                const uint32_t n_g = __builtin_amdgcn_readlane(v_n, g);
+                const uint64_t off_g = n8_readlane_u64(v_off, g);
+                const bool valid = (uint32_t)lane < n_g;
+                const bool ex = (noR | n8_excl(c[g], th0, th1, th2, th3)) != 0u;
+                const bool mine = valid & !ex;
+                const uint64_t exm = ballot(valid & ex);
+                const uint32_t cnt = (uint32_t)__builtin_popcountll(ballot(mine));
+                const uint32_t fx = exm ? (uint32_t)__builtin_ctzll(exm) : 0xFFFFFFFFu;
+                ev[g] = n8_load_eff(l_eff, off_g, mine,
+                                    reinterpret_cast<const int64_t *>(R + (i0 + (uint64_t)g) * 8u));
+                // LastOpCt's terms in place of the row: the included op's deltas
+                c[g].x = mine ? c[g].x : 0u;
+                c[g].y = mine ? c[g].y : 0u;
+                c[g].z = mine ? c[g].z : 0u;
+                c[g].w = mine ? c[g].w : 0u;
+                v_inc |= mine ? (1u << g) : 0u;
+                __builtin_amdgcn_sched_barrier(0);  // key g's effects go out before key g + 1's verdict
+                cg = kg == g ? cnt : cg;
+                v_cnt = put_lane(cnt, g, v_cnt);
+                v_fx = put_lane(fx, g, v_fx);
+            }
+            __builtin_amdgcn_sched_barrier(0);  // the eight effect loads are in flight from here
+            // The pointers the results need are read here, under the effects
+            // (k_counter_quad2).  Where the log has no id index, lanes 0-7 load
+            // the op id that defines their request's NewLastOp -- one load; the
+            // other lanes read an address the wave has fetched.
+            const auto &pr = kparams<Q2Params>();
+            const uint32_t *const l_op_id = pr.op_id;
+            int64_t *const l_value = pr.o_value, *const l_hole = pr.o_hole;
+            uint64_t *const l_lastct = pr.o_lastct;
+            uint32_t *const l_count = pr.o_count, *const l_flags = pr.o_flags, *const l_err = pr.o_err;
+            const int32_t fx = (int32_t)v_fx;
+            const uint32_t pos = fx >= 0 ? (uint32_t)fx : v_n - 1u;
+            const bool need = lane < 8 && v_id0 == AGN_ID0_NONE && v_n != 0u;
+            const uint32_t *const ip = need ? l_op_id + (v_off + (uint64_t)pos)
+                                            : reinterpret_cast<const uint32_t *>(R + slot);
+            const uint32_t opid = *ip;
+            // LastOpCt = base + max delta where the key included an op, else 0 (cold)
+            const uint32_t md = n8_maxfold(c);
+            const uint64_t ct = cg ? bv + (uint64_t)md : 0ull;
+            __builtin_amdgcn_sched_barrier(0);  // the wait for the effects: after the fold
+            uint64_t sm[8];
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const bool mine = ((v_inc >> g) & 1u) != 0u;
+                const bool badv = mine && ev[g] == AGN_EFFECT_INVALID;
+                const uint64_t be = ballot(badv);
+                v_fe = put_lane(be ? (uint32_t)__builtin_ctzll(be) : 0xFFFFFFFFu, g, v_fe);
+                sm[g] = (mine && !badv) ? (uint64_t)ev[g] : 0ull;
+            }
+            // key (lane >> 3)'s sum in every lane; lane g < 8 takes key g's
+            const uint64_t ks = n8_sumfold(sm);
+            const uint64_t total =
+                ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ks >> 32), 8 * (int)m8, AGN_WAVE) << 32) |
+                (uint32_t)__shfl((int)(uint32_t)ks, 8 * (int)m8, AGN_WAVE);
+            __builtin_amdgcn_sched_barrier(0);  // and no store before it
+            // lane g < 8: request g's result, as q2_result's of a cold read
+            const uint64_t idh = v_id0 != AGN_ID0_NONE ? (uint64_t)v_id0 + (uint64_t)pos : (uint64_t)opid;
+            const int64_t hid = v_n ? (int64_t)idh : 0;  // get_first_id of no ops: 0
+            const int32_t fe = (int32_t)v_fe;
+            uint32_t fl = v_cnt ? AGN_F_NEWSS : AGN_F_CT_IGNORE;
+            fl |= fe >= 0 ? AGN_F_ERR_UNEXPECTED : 0u;
+            l_lastct[slot] = ct;  // the eight rows: 512 contiguous bytes
+            if (lane < 8) {  // one store per array
+                const uint64_t i = i0 + (uint64_t)lane;
+                l_value[i] = (int64_t)(reqbase + total);
+                l_hole[i] = fx >= 0 ? hid - 1 : hid;
+                l_count[i] = v_cnt;
+                l_err[i] = fe >= 0 ? (uint32_t)(v_off + (uint64_t)fe) : 0xffffffffu;
+                l_flags[i] = fl;
+            }
+            return;
+        }
+    }
+    const uint64_t left = a.n_req - i0;
+    const uint32_t m = left < 8u ? (uint32_t)left : 8u;
+#pragma nounroll
+    for (uint32_t h = 0; h < m; ++h) q2_serve_oc(a, i0 + h);
+}
+
 // ROWS_QUAD with the first chunk EARLY (D = 8, one request per wave; the
 // sparse batches, MSK): the key's segment metadata (key_off, key_len,
 // key_id0) is the only scalar round trip before the rows -- chunk 0's quad
@@ -1691,7 +1893,27 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
     const char *fv = AGN_KNOB("AGN_Q2_FOUR");
     const bool four = pack && !req.keys && log.n_entries / 64u <= log.n_keys &&
                       ((fv && (fv[0] == '0' || fv[0] == '1')) ? fv[0] == '1' : Q2_FOUR_DEFAULT);
-    if (four) {
+    // AGN_Q2_NARROW = 0|1 (A/B knob, default on): that read over a log whose
+    // index has a narrow tier (agn_log_index_pack16) with nearly every key
+    // narrow runs eight requests per wave over the u16 rows, k_counter_pack8.
+    // Set to 1 it takes the kernel whatever the count of wide keys (the bound
+    // is a matter of speed, not of results; the tests reach the kernel's
+    // fallback on small logs this way).
+    const char *nv = AGN_KNOB("AGN_Q2_NARROW");
+    const bool eight = four && pk.rows16 && pk.narrow &&
+                       ((nv && (nv[0] == '0' || nv[0] == '1'))
+                            ? nv[0] == '1'
+                            : pk.n_wide * NARROW_WIDE_DIV <= log.n_keys);
+    if (eight) {
+        a.xcd = counter_order(req.n_req, BULK_CHUNK8);
+        const Q2Pack8Params p{a, mk,
+                              {req.keys, log.key_off, log.key_len, log.key_type, id0_index(log),
+                               log.oc, log.op_id, log.eff, log.txid, req.R, req.sct, req.sct_ignore,
+                               req.txid, req.base_value, out.value, out.hole, out.lastct, out.count,
+                               out.flags, out.err_pos},
+                              pk.rows, pk.base, pk.ok, pk.rows16, pk.narrow};
+        hipLaunchKernelGGL(k_counter_pack8, dim3((unsigned)((req.n_req + 7) / 8)), dim3(64), 0, st, p);
+    } else if (four) {
         a.xcd = counter_order(req.n_req, BULK_CHUNK4);
         const Q2PackParams p{a, mk,
                              {req.keys, log.key_off, log.key_len, log.key_type, id0_index(log),
@@ -2085,7 +2307,90 @@ __global__ __launch_bounds__(256) void k_index_pack(const uint64_t *__restrict__
         atomicAdd(&unpacked[(blockIdx.x % IM_CNT) * IM_STRIDE], (unsigned long long)blk_un);
 }
 
+// agn_log_index_pack16: one wave per key, from the u32 index.  Pass 1 decides
+// whether the key is narrow -- packed, and no u32 delta above 2^16 - 1 (lane =
+// entry) -- pass 2 writes a narrow key's u16 deltas: lane l stores the 16-byte
+// unit of entry b + l, the layout n8_load_rows reads.  The block's wide keys
+// are counted as k_index_pack counts its unpacked ones.
+__global__ __launch_bounds__(256) void k_index_pack16(const uint64_t *__restrict__ key_off,
+                                                     const uint64_t *__restrict__ key_len,
+                                                     const uint32_t *__restrict__ rows,
+                                                     const uint8_t *__restrict__ ok, uint64_t n_keys,
+                                                     uint16_t *__restrict__ rows16,
+                                                     uint8_t *__restrict__ narrow,
+                                                     unsigned long long *__restrict__ wide) {
+    __shared__ uint32_t blk_w;
+    if (threadIdx.x == 0) blk_w = 0;
+    __syncthreads();
+    const uint64_t k = uniform_u64((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6));
+    const int lane = lane_id();
+    if (k < n_keys) {
+        const uint64_t off = key_off[k];
+        const uint64_t n = key_len ? key_len[k] : key_off[k + 1] - off;
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(rows);
+        bool fits = ok[k] != 0;
+        for (uint64_t b = 0; fits && b < n; b += AGN_WAVE) {
+            const uint64_t p = b + (uint64_t)lane;
+            bool big = false;
+            if (p < n) {
+                const u32x4 lo = src[(off + p) * 2u], hh = src[(off + p) * 2u + 1u];
+                big = ((lo.x | lo.y | lo.z | lo.w | hh.x | hh.y | hh.z | hh.w) >> 16) != 0u;
+            }
+            fits = ballot(big) == 0ull;
+        }
+        if (lane == 0) {
+            narrow[k] = fits ? 1 : 0;
+            if (!fits) atomicAdd(&blk_w, 1u);
+        }
+        if (fits) {
+            for (uint64_t b = 0; b < n; b += AGN_WAVE) {
+                const uint64_t p = b + (uint64_t)lane;
+                if (p < n) {
+                    const u32x4 lo = src[(off + p) * 2u], hh = src[(off + p) * 2u + 1u];
+                    u32x4 v;
+                    v.x = lo.x | (lo.y << 16);
+                    v.y = lo.z | (lo.w << 16);
+                    v.z = hh.x | (hh.y << 16);
+                    v.w = hh.z | (hh.w << 16);
+                    reinterpret_cast<u32x4 *>(rows16)[off + p] = v;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && blk_w)
+        atomicAdd(&wide[(blockIdx.x % IM_CNT) * IM_STRIDE], (unsigned long long)blk_w);
+}
+
 }  // namespace
+
+int launch_index_pack16(const agn_log &log, const uint32_t *rows, const uint8_t *ok,
+                        uint16_t *rows16, uint8_t *narrow, uint64_t *n_wide, hipStream_t st) {
+    const uint64_t nb = (log.n_keys + 3) / 4;
+    *n_wide = 0;
+    if (nb == 0) return AGN_OK;
+    if (nb > 0x7fffffffull) return fail(AGN_EINVAL, "index_pack16: too many keys");
+    unsigned long long *cnt = nullptr;
+    const size_t cb = (size_t)IM_CNT * IM_STRIDE * sizeof(unsigned long long);
+    AGN_HIP(pool_malloc(&cnt, cb, st));
+    if (hipMemsetAsync(cnt, 0, cb, st) != hipSuccess) {
+        (void)hipFreeAsync(cnt, st);
+        return fail(AGN_EHIP, "index_pack16: counter reset");
+    }
+    hipLaunchKernelGGL(k_index_pack16, dim3((unsigned)nb), dim3(256), 0, st, log.key_off,
+                       log.key_len, rows, ok, log.n_keys, rows16, narrow, cnt);
+    int rc = hipGetLastError() == hipSuccess ? AGN_OK : fail(AGN_EHIP, "index_pack16: launch");
+    // the count is read back here: the call blocks until the tier is built
+    std::vector<unsigned long long> h((size_t)IM_CNT * IM_STRIDE);
+    if (rc == AGN_OK &&
+        (hipMemcpyAsync(h.data(), cnt, cb, hipMemcpyDeviceToHost, st) != hipSuccess ||
+         hipStreamSynchronize(st) != hipSuccess))
+        rc = fail(AGN_EHIP, "index_pack16: wide-key count");
+    if (rc == AGN_OK)
+        for (uint32_t i = 0; i < IM_CNT; ++i) *n_wide += h[(size_t)i * IM_STRIDE];
+    (void)hipFreeAsync(cnt, st);
+    return rc;
+}
 
 int launch_index_pack(const agn_log &log, uint32_t *rows, uint64_t *base, uint8_t *ok,
                       uint64_t *n_unpacked, hipStream_t st) {

@@ -154,6 +154,27 @@ class Engine:
             dlog.bufs.update(pack_rows=rows, pack_base=base, pack_ok=ok)
         return rows, base, ok, (n.value if count else None)
 
+    def index_pack16(self, dlog, stream=None):
+        """Build and register the narrow tier of a device log's packed index
+        (agn_log_index_pack16; index_pack first); returns (rows16, narrow,
+        n_wide) -- the buffers are owned by dlog when dlog is DeviceArrays."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        K, E = int(ls.n_keys), int(ls.n_entries)
+        rows16, narrow = self.empty(max(1, E) * 16), self.empty(max(1, (K + 7) // 8) * 8)
+        n = C.c_uint64(0)
+        check(self.lib.agn_log_index_pack16(self.ctx, C.byref(ls), rows16.ptr, narrow.ptr,
+                                            C.byref(n), stream),
+              "agn_log_index_pack16")
+        if isinstance(dlog, DeviceArrays):
+            dlog.bufs.update(pack_rows16=rows16, pack_narrow=narrow)
+        return rows16, narrow, n.value
+
+    def drop_pack16(self, dlog):
+        """Drop the narrow tier alone (agn_log_index_pack16, rows16 = NULL)."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        check(self.lib.agn_log_index_pack16(self.ctx, C.byref(ls), None, None, None, None),
+              "agn_log_index_pack16")
+
     def drop_pack(self, dlog):
         """Drop the log's packed-index registration (agn_log_index_pack, rows = NULL)."""
         ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog

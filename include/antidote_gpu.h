@@ -333,6 +333,40 @@ int agn_log_index_masks(agn_ctx *ctx, const agn_log *log, uint64_t *out, void *s
 int agn_log_index_pack(agn_ctx *ctx, const agn_log *log, uint32_t *rows, uint64_t *base,
                        uint8_t *ok, uint64_t *n_unpacked, void *stream);
 
+/* The narrow tier of the packed index: the rows of the keys whose every column
+ * spans at most 2^16 - 1 as u16 deltas against the same column minima (base),
+ * 16 bytes per op -- a quarter of oc, half of `rows`.  A key is narrow only if
+ * its whole segment lies within 65 ms of microsecond clock per column: hot
+ * keys (bursts) and the columns of DCs that did not move, not the typical key
+ * of a partition, so the tier sits on top of the u32 index, which stays
+ * complete, and a read takes it only when nearly the whole log is narrow.
+ *   narrow[k] ([n_keys] u8, in an allocation of whole dwords padded to a
+ *     multiple of 8 keys) = 1 iff ok[k] == 1 and every column of key k spans at
+ *     most 65 535 (empty keys: 1);
+ *   rows16[e][d] ([n_entries][8] u16, entry-major: a 64-op key is 1 KiB, entry
+ *     off + l one 16-byte unit) = oc[e][d] - base[k][d] for the entries of keys
+ *     with narrow == 1, unspecified otherwise.
+ * The caller owns both device buffers (rows16 16-byte, narrow 4-byte aligned).
+ * The log must have a registered u32 index (agn_log_index_pack, same key: oc,
+ * key_off, n_entries, n_keys), from which the tier is built; the call always
+ * counts the keys with narrow == 0 and blocks until the tier is built (as
+ * agn_log_index_masks does), keeps the count in the registration and returns
+ * it through n_wide (may be NULL).  A cold dense whole-partition
+ * agn_materialize / agn_tune (req.keys == NULL) of a log of at most 64 entries
+ * per key on average, of whose keys at most one in 1024 is not narrow, then
+ * scans rows16 for every aligned group of eight requests whose keys are all
+ * narrow, at most 64 entries long and of the request's type; every other group
+ * reads oc, and every other read is served as without the tier.  Results never
+ * depend on it.  rows16 == NULL drops the narrow tier only (nothing else is
+ * read then), and so does agn_dev_free of rows16 or narrow; registering the
+ * u32 index again, dropping it, agn_close and eviction drop both tiers.
+ * AGN_ENOTSUP: as agn_log_index_pack; AGN_EINVAL: no u32 index registered for
+ * the log, a missing or misaligned array.  Environment AGN_Q2_NARROW=0 keeps
+ * reads off the tier, =1 takes it whatever the count of wide keys (A/B knob).
+ * An addition to ABI v7: no struct changed, the version number stays. */
+int agn_log_index_pack16(agn_ctx *ctx, const agn_log *log, uint16_t *rows16, uint8_t *narrow,
+                         uint64_t *n_wide, void *stream);
+
 /* Upper bound of live pairs per request for set/register types:
  * writes cap_off[n_req+1] (host pointers): cap = #adding entries of the key
  * + #base pairs.  Host-side helper (the bound is static per log): every
