@@ -150,6 +150,7 @@ PROTOTYPES = {
     "agn_log_index_masks": (C.c_int, [P, C.POINTER(AgnLog), P, P]),
     "agn_log_index_pack": (C.c_int, [P, C.POINTER(AgnLog), P, P, P, C.POINTER(C.c_uint64), P]),
     "agn_log_index_pack16": (C.c_int, [P, C.POINTER(AgnLog), P, P, C.POINTER(C.c_uint64), P]),
+    "agn_log_index_eff16": (C.c_int, [P, C.POINTER(AgnLog), P, C.POINTER(C.c_uint64), P]),
     "agn_tune": (C.c_int, [P, C.POINTER(AgnLog), C.POINTER(AgnRead), C.POINTER(AgnResult), P,
                            C.c_int, C.POINTER(C.c_int), P]),
     "agn_select_base": (C.c_int, [P, C.c_uint32, C.c_uint64, P, P, P, P, P, P, P, P]),
@@ -230,7 +231,7 @@ ORACLE_PROTOTYPES = {
 # Additions to ABI v7 (no struct changed, the version number stayed): a library
 # built before them still loads -- an A/B against an earlier build of the same
 # ABI through AGN_LIB -- and calling a missing one raises AttributeError.
-ADDITIVE = frozenset({"agn_log_index_pack16"})
+ADDITIVE = frozenset({"agn_log_index_pack16", "agn_log_index_eff16"})
 
 
 def bind(lib, protos):

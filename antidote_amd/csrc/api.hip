@@ -192,6 +192,7 @@ struct PackEnt {
     PackIdx idx;
     bool owned;  // agn_gen_dev's buffers: freed with the entry
     bool owned16;  // and the narrow tier's (idx.rows16, idx.narrow)
+    bool owned_e;  // and the effect tier's (idx.eff16)
 };
 constexpr int kPackIdx = 16;
 std::mutex g_pk_mu;
@@ -199,8 +200,19 @@ PackEnt g_pk[kPackIdx] = {};
 uint64_t g_pk_seq = 0;
 std::atomic<int> g_pk_live{0};
 
-// The entry's narrow tier alone (agn_log_index_pack16): the u32 index stays.
+// The entry's effect tier alone (agn_log_index_eff16): the other tiers stay.
+void pack_drop_eff_locked(PackEnt &e) {
+    if (e.owned_e) (void)hipFree((void *)e.idx.eff16);
+    e.idx.eff16 = nullptr;
+    e.idx.eff_src = nullptr;
+    e.idx.n_esc = 0;
+    e.owned_e = false;
+}
+
+// The entry's narrow tier (agn_log_index_pack16) and the effect tier on top of
+// it: the u32 index stays.
 void pack_drop16_locked(PackEnt &e) {
+    pack_drop_eff_locked(e);
     if (e.owned16) {
         (void)hipFree((void *)e.idx.rows16);
         (void)hipFree((void *)e.idx.narrow);
@@ -250,7 +262,7 @@ void pack_register(agn_ctx *ctx, const agn_log &log, const PackIdx &idx, bool ow
             if (e.seq < slot->seq) slot = &e;
     }
     pack_drop_locked(*slot);
-    *slot = {ctx, log.oc, log.key_off, log.n_entries, log.n_keys, ++g_pk_seq, idx, owned, false};
+    *slot = {ctx, log.oc, log.key_off, log.n_entries, log.n_keys, ++g_pk_seq, idx, owned, false, false};
     g_pk_live.fetch_add(1, std::memory_order_release);
 }
 
@@ -279,6 +291,31 @@ bool pack_register16(const agn_log &log, const uint16_t *rows16, const uint8_t *
     return false;
 }
 
+// Drop the effect tier of the log's entry, if any.
+void pack_unregister_eff(const agn_log &log) {
+    if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (pack_match(e, log)) pack_drop_eff_locked(e);
+}
+
+// Attach an effect tier to the log's entry (replacing one); false when the
+// entry or its narrow tier is gone (dropped or evicted since the caller
+// looked it up).
+bool pack_register_eff(const agn_log &log, const int16_t *eff16, uint64_t n_esc, bool owned) {
+    std::lock_guard<std::mutex> g(g_pk_mu);
+    for (auto &e : g_pk)
+        if (pack_match(e, log) && e.idx.rows16) {
+            pack_drop_eff_locked(e);
+            e.idx.eff16 = eff16;
+            e.idx.eff_src = log.eff;
+            e.idx.n_esc = n_esc;
+            e.owned_e = owned;
+            return true;
+        }
+    return false;
+}
+
 // agn_close: the context's entries.
 void pack_clear(agn_ctx *ctx) {
     if (g_pk_live.load(std::memory_order_relaxed) == 0) return;
@@ -297,6 +334,8 @@ void pack_forget(const void *p) {
             pack_drop_locked(e);
         else if (e.idx.rows16 && (p == e.idx.rows16 || p == e.idx.narrow))
             pack_drop16_locked(e);  // the narrow tier alone: the u32 index stays
+        else if (e.idx.eff16 && (p == e.idx.eff16 || p == e.idx.eff_src))
+            pack_drop_eff_locked(e);  // the effect tier alone
     }
 }
 }  // namespace
@@ -616,6 +655,34 @@ int agn_log_index_pack16(agn_ctx *ctx, const agn_log *log, uint16_t *rows16, uin
     if (n_wide) *n_wide = wide;
     if (!pack_register16(*log, rows16, narrow, wide, false))
         return fail(AGN_EINVAL, "index_pack16: the log's packed index was dropped meanwhile");
+    return AGN_OK;
+}
+
+int agn_log_index_eff16(agn_ctx *ctx, const agn_log *log, int16_t *eff16, uint64_t *n_escaped,
+                        void *stream) {
+    if (!log) return fail(AGN_EINVAL, "index_eff16: null log");
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if (n_escaped) *n_escaped = 0;
+    if (!eff16) {  // drop the effect tier; the other tiers stay registered
+        pack_unregister_eff(*log);
+        return AGN_OK;
+    }
+    if (log->crdt_type != AGN_COUNTER_PN || log->n_dcs != 8 || log->oc_mask)
+        return fail(AGN_ENOTSUP, "index_eff16: counter_pn logs with 8 dense DCs only");
+    if (!log->eff) return fail(AGN_EINVAL, "index_eff16: eff required");
+    // the build kernel stores eff16 as 16-byte units
+    if ((uintptr_t)eff16 & 15u) return fail(AGN_EINVAL, "index_eff16: eff16 16-byte aligned");
+    PackIdx pk{};
+    if (!pack_lookup(*log, &pk) || !pk.rows16)
+        return fail(AGN_EINVAL, "index_eff16: no narrow tier registered for the log "
+                                "(agn_log_index_pack16 first)");
+    uint64_t esc = 0;
+    rc = launch_index_eff16(*log, eff16, &esc, (hipStream_t)stream);
+    if (rc) return rc;
+    if (n_escaped) *n_escaped = esc;
+    if (!pack_register_eff(*log, eff16, esc, false))
+        return fail(AGN_EINVAL, "index_eff16: the log's narrow tier was dropped meanwhile");
     return AGN_OK;
 }
 
@@ -1466,6 +1533,19 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
                 (void)hipStreamSynchronize(s);
                 if (p16) (void)hipFree(p16);
                 if (pn) (void)hipFree(pn);
+            }
+            // and the effect tier on top of it (agn_log_index_eff16): without
+            // it the log keeps the tiers it has
+            void *pe = nullptr;
+            uint64_t esc = 0;
+            const bool etier =
+                tier && hipMalloc(&pe, (E + 7) / 8 * 8 * sizeof(int16_t)) == hipSuccess &&
+                launch_index_eff16(*log, (int16_t *)pe, &esc, s) == AGN_OK &&
+                pack_register_eff(*log, (const int16_t *)pe, esc, true);
+            if (tier && !etier) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(s);
+                if (pe) (void)hipFree(pe);
             }
         } else {
             (void)hipGetLastError();

@@ -320,6 +320,12 @@ struct PackIdx {
     const uint16_t *rows16;
     const uint8_t *narrow;
     uint64_t n_wide;
+    // Its effect tier (agn_log_index_eff16; absent: eff16 == nullptr): i16
+    // effects [n_entries] with the escape 0x8000, the eff array they were
+    // built from, and the count of escaped entries.
+    const int16_t *eff16;
+    const int64_t *eff_src;
+    uint64_t n_esc;
 };
 // n_unpacked (optional): the count of unpacked keys, read back (blocks).
 int launch_index_pack(const agn_log &log, uint32_t *rows, uint64_t *base, uint8_t *ok,
@@ -328,6 +334,9 @@ int launch_index_pack(const agn_log &log, uint32_t *rows, uint64_t *base, uint8_
 // read back (always: the call blocks).
 int launch_index_pack16(const agn_log &log, const uint32_t *rows, const uint8_t *ok,
                         uint16_t *rows16, uint8_t *narrow, uint64_t *n_wide, hipStream_t st);
+// The effect tier from log.eff; *n_esc: the escaped entries, read back
+// (always: the call blocks).
+int launch_index_eff16(const agn_log &log, int16_t *eff16, uint64_t *n_esc, hipStream_t st);
 // The index registered for this log (api.hip; the launchers carry no
 // context, so the table is the process's, each entry owned by a context);
 // *out is written only when one is found.

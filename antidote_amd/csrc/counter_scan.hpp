@@ -674,6 +674,40 @@ __device__ __forceinline__ uint64_t n8_sumfold(const uint64_t (&s)[8]) {
     return v;
 }
 
+// The effect tier's i16 of entry off + lane (agn_log_index_eff16), as its 16
+// bits, under n8_load_rows' clamp: a 64-op key is one 128-byte line.
+__device__ __forceinline__ uint32_t n8_load_eff16(const int16_t *__restrict__ eff16, uint64_t off,
+                                                  uint64_t n_entries) {
+    // min(off + lane, n_entries - 1) as a wave-uniform base plus a 32-bit lane
+    // offset: one address VGPR per load
+    const uint64_t last = n_entries - 1u;
+    const uint64_t o = off < last ? off : last;
+    const uint32_t room = last - o < 63u ? (uint32_t)(last - o) : 63u;
+    const uint32_t l = (uint32_t)lane_id() < room ? (uint32_t)lane_id() : room;
+    return (uint32_t)ld<true>(reinterpret_cast<const uint16_t *>(eff16) + o + l);
+}
+
+// n8_sumfold for u32 terms (the effect tier's: 64 terms of magnitude at most
+// 32 767 fit an i32): half the registers and half the shuffles.  Lane l holds
+// the sum of key l >> 3 mod 2^32.
+__device__ __forceinline__ uint32_t n8_sumfold32(const uint32_t (&s)[8]) {
+    const int lane = lane_id();
+    auto xch = [](uint32_t keep, uint32_t send, int stride) {
+        return keep + (uint32_t)__shfl_xor((int)send, stride, AGN_WAVE);
+    };
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
+    uint32_t v4[4], v2[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v4[k] = xch(b5 ? s[4 + k] : s[k], b5 ? s[k] : s[4 + k], 32);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) v2[k] = xch(b4 ? v4[2 + k] : v4[k], b4 ? v4[k] : v4[2 + k], 16);
+    uint32_t v = xch(b3 ? v2[1] : v2[0], b3 ? v2[0] : v2[1], 8);
+    v += __builtin_amdgcn_update_dpp(0u, v, 0xB1, 0xF, 0xF, false);   // quad_perm 1,0,3,2
+    v += __builtin_amdgcn_update_dpp(0u, v, 0x4E, 0xF, 0xF, false);   // quad_perm 2,3,0,1
+    v += __builtin_amdgcn_update_dpp(0u, v, 0x141, 0xF, 0xF, false);  // row_half_mirror
+    return v;
+}
+
 // Wave-uniform groups of per-key metadata as one scalar load each: the arrays
 // are aligned to their elements only.
 typedef unsigned long long u64x4 __attribute__((ext_vector_type(4)));

@@ -68,6 +68,18 @@ constexpr bool Q2_FOUR_DEFAULT = true;
 // profiles/r11/ab_narrow_bound.log), so the bound stands as estimated.
 constexpr uint32_t BULK_CHUNK8 = 64;
 constexpr uint64_t NARROW_WIDE_DIV = 1024;
+// k_counter_pack8<true> (the effect tier, agn_log_index_eff16): whether the
+// launcher takes it without AGN_Q2_EFF16 set, and its bound on the log's
+// escaped entries: at most one entry in EFF16_ESC_DIV may hold the escape (a
+// group whose included ops hold one takes the kernel's branch to `eff`).
+// Cold cfg2 in one process 2.373 ms with the tier against 2.707 without
+// (profiles/r12/ab_q2_eff16.log).  At the bound, 1M keys x 64 ops with one
+// entry in 1024 escaped, evenly spread, 0.257 against 0.289 ms (1.12x; one in
+// 256: 1.16x; one in 64, an escape in every key: 1.12x;
+// profiles/r12/ab_eff_bound.log): the tier did not lose at any density
+// measured, and the bound stands as estimated.
+constexpr bool EFF16_DEFAULT = true;
+constexpr uint64_t EFF16_ESC_DIV = 1024;
 
 struct DenseArgs {
     uint64_t n_req;
@@ -1457,6 +1469,7 @@ struct Q2Pack8Params {
     const uint8_t *ok;
     const uint16_t *rows16;
     const uint8_t *narrow;
+    const int16_t *eff16;  // the effect tier (agn_log_index_eff16); E16 only
 };
 static_assert(offsetof(Q2Pack8Params, rows) == offsetof(Q2PackParams, rows) &&
                   offsetof(Q2Pack8Params, base) == offsetof(Q2PackParams, base),
@@ -1482,6 +1495,19 @@ static_assert(offsetof(Q2Pack8Params, rows) == offsetof(Q2PackParams, rows) &&
 // the last one of a batch that is no multiple of eight, which reads nothing
 // past request n_req - 1 -- runs its requests one after the other through oc
 // (q2_serve_oc).  Same results as k_counter_quad2.
+//
+// E16: over the effect tier (agn_log_index_eff16).  Each key's i16 effects --
+// one 128-byte line of a 64-op key -- are loaded with its rows, before any
+// verdict: sixteen loads in flight, two dependent round trips (metadata ->
+// rows and effects -> stores) where the 8-byte gathers of `eff` make a third.
+// The included lanes' terms are i32 (64 terms of magnitude at most 32 767), so
+// the sums fold as u32 (n8_sumfold32) and are sign-extended once per key.  An
+// included lane that holds the escape 0x8000 sets bit g of v_esc; one
+// wave-uniform branch after the fold (rare: the launcher bounds the log's
+// escapes) reads those lanes' `eff`, where alone an AGN_EFFECT_INVALID can be
+// met, and adds their i64 sum.  The op id is loaded only when a lane needs
+// one: a non-empty key without an id base (no id index, or AGN_ID0_NONE in it).
+template <bool E16>
 __global__ __launch_bounds__(64) void k_counter_pack8(Q2Pack8Params) {
     const DenseArgs a = dense_of(kparams<Q2Params>().a);
     const uint32_t blk = block_order(a.xcd, blockIdx.x, gridDim.x);
@@ -1539,7 +1565,15 @@ __global__ __launch_bounds__(64) void k_counter_pack8(Q2Pack8Params) {
             for (int g = 0; g < 8; ++g)
                 c[g] = n8_load_rows<true>(rows16, n8_readlane_u64(v_off, g), a.n_entries);
             const int64_t *const l_eff = kparams<Q2Params>().eff;
-            // all eight row loads are in flight before the first verdict
+            uint32_t e16[E16 ? 8 : 1];  // E16 only: written and read under if constexpr (E16)
+            if constexpr (E16) {
+                const int16_t *const eff16 = kparams<Q2Pack8Params>().eff16;
+#pragma unroll
+                for (int g = 0; g < 8; ++g)
+                    e16[g] = n8_load_eff16(eff16, n8_readlane_u64(v_off, g), a.n_entries);
+            }
+            // all eight row loads (E16: all sixteen loads) are in flight before
+            // the first verdict
             __builtin_amdgcn_sched_barrier(0);
             // thresholds min(R - base, 2^16 - 1); noR of key g: its 8 lanes' bits
             const uint64_t below = ballot(rv < bv);
@@ -1547,10 +1581,10 @@ __global__ __launch_bounds__(64) void k_counter_pack8(Q2Pack8Params) {
             const uint32_t tp = n8_thr_pack(dl > 0xFFFFull ? 0xFFFFu : (uint32_t)dl);
             // first_excl and first_err are positions < 64 or -1; request g's go
             // to lane g, the lanes' own verdicts to bit g of v_inc
-            uint32_t v_cnt = 0, v_fx = 0, v_fe = 0, v_inc = 0;
+            uint32_t v_cnt = 0, v_fx = 0, v_fe = E16 ? 0xFFFFFFFFu : 0u, v_inc = 0;
             uint32_t cg = 0;  // the count of key lane >> 3, this lane's key
             const int kg = lane >> 3;
-            int64_t ev[8];
+            int64_t ev[E16 ? 1 : 8];  // !E16 only: written and read under if constexpr (!E16)
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
                 const uint32_t th0 = __builtin_amdgcn_readlane(tp, 8 * g);
@@ -1566,8 +1600,9 @@ __global__ __launch_bounds__(64) void k_counter_pack8(Q2Pack8Params) {
                 const uint64_t exm = ballot(valid & ex);
                 const uint32_t cnt = (uint32_t)__builtin_popcountll(ballot(mine));
                 const uint32_t fx = exm ? (uint32_t)__builtin_ctzll(exm) : 0xFFFFFFFFu;
-                ev[g] = n8_load_eff(l_eff, off_g, mine,
-                                    reinterpret_cast<const int64_t *>(R + (i0 + (uint64_t)g) * 8u));
+                if constexpr (!E16)
+                    ev[g] = n8_load_eff(l_eff, off_g, mine,
+                                        reinterpret_cast<const int64_t *>(R + (i0 + (uint64_t)g) * 8u));
                 // LastOpCt's terms in place of the row: the included op's deltas
                 c[g].x = mine ? c[g].x : 0u;
                 c[g].y = mine ? c[g].y : 0u;
@@ -1594,25 +1629,67 @@ __global__ __launch_bounds__(64) void k_counter_pack8(Q2Pack8Params) {
             const bool need = lane < 8 && v_id0 == AGN_ID0_NONE && v_n != 0u;
             const uint32_t *const ip = need ? l_op_id + (v_off + (uint64_t)pos)
                                             : reinterpret_cast<const uint32_t *>(R + slot);
-            const uint32_t opid = *ip;
+            // E16: nothing hides a dummy's round trip, so the load is issued
+            // only when some lane needs its op id (wave-uniform)
+            uint32_t opid = 0;
+            if (!E16 || ballot(need) != 0ull) opid = *ip;
+            // E16: the i32 terms and their fold first -- the effects came in
+            // with the rows, and eight registers are one before the max fold
+            uint32_t v_esc = 0, ks32 = 0;
+            if constexpr (E16) {
+                uint32_t sm[8];
+#pragma unroll
+                for (int g = 0; g < 8; ++g) {
+                    const bool mine = ((v_inc >> g) & 1u) != 0u;
+                    const bool esc = mine && e16[g] == 0x8000u;
+                    v_esc |= esc ? (1u << g) : 0u;
+                    sm[g] = (mine && !esc) ? (uint32_t)(int32_t)(int16_t)e16[g] : 0u;
+                }
+                // key (lane >> 3)'s i32 sum in every lane
+                ks32 = n8_sumfold32(sm);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             // LastOpCt = base + max delta where the key included an op, else 0 (cold)
             const uint32_t md = n8_maxfold(c);
             const uint64_t ct = cg ? bv + (uint64_t)md : 0ull;
             __builtin_amdgcn_sched_barrier(0);  // the wait for the effects: after the fold
-            uint64_t sm[8];
+            uint64_t total;
+            if constexpr (E16) {
+                // lane g < 8 takes key g's sum, sign-extended once
+                total = (uint64_t)(int64_t)(int32_t)__shfl((int)ks32, 8 * (int)m8, AGN_WAVE);
+                if (ballot(v_esc != 0u) != 0ull) {
+                    // the escaped lanes (and only they) read eff; lane g takes
+                    // key g's first invalid position and the others' i64 sum
+#pragma nounroll
+                    for (int g = 0; g < 8; ++g) {
+                        const bool esc = ((v_esc >> g) & 1u) != 0u;
+                        if (ballot(esc) == 0ull) continue;
+                        const uint64_t off_g = n8_readlane_u64(v_off, g);
+                        int64_t x = 0;
+                        if (esc) x = l_eff[off_g + (uint64_t)lane];
+                        const bool badv = esc && x == AGN_EFFECT_INVALID;
+                        const uint64_t be = ballot(badv);
+                        const uint64_t xs = (uint64_t)wave_sum_dpp(badv ? 0 : x);
+                        v_fe = put_lane(be ? (uint32_t)__builtin_ctzll(be) : 0xFFFFFFFFu, g, v_fe);
+                        total += lane == g ? xs : 0ull;
+                    }
+                }
+            } else {
+                uint64_t sm[8];
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const bool mine = ((v_inc >> g) & 1u) != 0u;
-                const bool badv = mine && ev[g] == AGN_EFFECT_INVALID;
-                const uint64_t be = ballot(badv);
-                v_fe = put_lane(be ? (uint32_t)__builtin_ctzll(be) : 0xFFFFFFFFu, g, v_fe);
-                sm[g] = (mine && !badv) ? (uint64_t)ev[g] : 0ull;
+                for (int g = 0; g < 8; ++g) {
+                    const bool mine = ((v_inc >> g) & 1u) != 0u;
+                    const bool badv = mine && ev[g] == AGN_EFFECT_INVALID;
+                    const uint64_t be = ballot(badv);
+                    v_fe = put_lane(be ? (uint32_t)__builtin_ctzll(be) : 0xFFFFFFFFu, g, v_fe);
+                    sm[g] = (mine && !badv) ? (uint64_t)ev[g] : 0ull;
+                }
+                // key (lane >> 3)'s sum in every lane; lane g < 8 takes key g's
+                const uint64_t ks = n8_sumfold(sm);
+                total =
+                    ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ks >> 32), 8 * (int)m8, AGN_WAVE) << 32) |
+                    (uint32_t)__shfl((int)(uint32_t)ks, 8 * (int)m8, AGN_WAVE);
             }
-            // key (lane >> 3)'s sum in every lane; lane g < 8 takes key g's
-            const uint64_t ks = n8_sumfold(sm);
-            const uint64_t total =
-                ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ks >> 32), 8 * (int)m8, AGN_WAVE) << 32) |
-                (uint32_t)__shfl((int)(uint32_t)ks, 8 * (int)m8, AGN_WAVE);
             __builtin_amdgcn_sched_barrier(0);  // and no store before it
             // lane g < 8: request g's result, as q2_result's of a cold read
             const uint64_t idh = v_id0 != AGN_ID0_NONE ? (uint64_t)v_id0 + (uint64_t)pos : (uint64_t)opid;
@@ -1904,6 +1981,17 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
                        ((nv && (nv[0] == '0' || nv[0] == '1'))
                             ? nv[0] == '1'
                             : pk.n_wide * NARROW_WIDE_DIV <= log.n_keys);
+    // AGN_Q2_EFF16 = 0|1 (A/B knob, AGN_Q2_NARROW's convention): the narrow
+    // read of a log with an effect tier (agn_log_index_eff16) built from this
+    // log.eff, of whose entries at most one in EFF16_ESC_DIV escaped, loads
+    // the i16 effects with the rows, k_counter_pack8<true>.  Set to 1 it takes
+    // the tier whatever the count of escapes (a matter of speed, not of
+    // results).
+    const char *xv = AGN_KNOB("AGN_Q2_EFF16");
+    const bool e16 = eight && pk.eff16 && log.eff == pk.eff_src &&
+                     ((xv && (xv[0] == '0' || xv[0] == '1'))
+                          ? xv[0] == '1'
+                          : EFF16_DEFAULT && pk.n_esc * EFF16_ESC_DIV <= log.n_entries);
     if (eight) {
         a.xcd = counter_order(req.n_req, BULK_CHUNK8);
         const Q2Pack8Params p{a, mk,
@@ -1911,8 +1999,10 @@ int launch_quad2(const agn_log &log, const agn_read &req, const agn_result &out,
                                log.oc, log.op_id, log.eff, log.txid, req.R, req.sct, req.sct_ignore,
                                req.txid, req.base_value, out.value, out.hole, out.lastct, out.count,
                                out.flags, out.err_pos},
-                              pk.rows, pk.base, pk.ok, pk.rows16, pk.narrow};
-        hipLaunchKernelGGL(k_counter_pack8, dim3((unsigned)((req.n_req + 7) / 8)), dim3(64), 0, st, p);
+                              pk.rows, pk.base, pk.ok, pk.rows16, pk.narrow, pk.eff16};
+        const dim3 grid((unsigned)((req.n_req + 7) / 8));
+        if (e16) hipLaunchKernelGGL(k_counter_pack8<true>, grid, dim3(64), 0, st, p);
+        else hipLaunchKernelGGL(k_counter_pack8<false>, grid, dim3(64), 0, st, p);
     } else if (four) {
         a.xcd = counter_order(req.n_req, BULK_CHUNK4);
         const Q2PackParams p{a, mk,
@@ -2362,7 +2452,76 @@ __global__ __launch_bounds__(256) void k_index_pack16(const uint64_t *__restrict
         atomicAdd(&wide[(blockIdx.x % IM_CNT) * IM_STRIDE], (unsigned long long)blk_w);
 }
 
+// agn_log_index_eff16: a grid-stride pass, eight entries per lane -- eight
+// 8-byte loads (eff is aligned to its elements only) and one 16-byte store;
+// the log's last entries, short of eight, one lane each.  An effect outside
+// [-32767, 32767] becomes the escape 0x8000; the block's escaped entries are
+// counted as k_index_pack16 counts its wide keys.
+__global__ __launch_bounds__(256) void k_index_eff16(const int64_t *__restrict__ eff,
+                                                    uint64_t n_entries,
+                                                    int16_t *__restrict__ eff16,
+                                                    unsigned long long *__restrict__ escaped) {
+    __shared__ uint32_t blk_e;
+    if (threadIdx.x == 0) blk_e = 0;
+    __syncthreads();
+    auto narrow16 = [](int64_t x, uint32_t &esc) {
+        const bool fits = x >= -32767 && x <= 32767;
+        esc += fits ? 0u : 1u;
+        return fits ? (uint32_t)x & 0xFFFFu : 0x8000u;
+    };
+    uint32_t esc = 0;
+    const uint64_t units = n_entries / 8u, stride = (uint64_t)gridDim.x * 256u;
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    for (uint64_t u = t; u < units; u += stride) {
+        int64_t x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = eff[u * 8u + (uint64_t)j];
+        uint32_t h[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) h[j] = narrow16(x[j], esc);
+        u32x4 v;
+        v.x = h[0] | (h[1] << 16);
+        v.y = h[2] | (h[3] << 16);
+        v.z = h[4] | (h[5] << 16);
+        v.w = h[6] | (h[7] << 16);
+        reinterpret_cast<u32x4 *>(eff16)[u] = v;
+    }
+    const uint64_t e = units * 8u + t;  // the tail: fewer than eight entries
+    if (e < n_entries) eff16[e] = (int16_t)(uint16_t)narrow16(eff[e], esc);
+    if (esc) atomicAdd(&blk_e, esc);
+    __syncthreads();
+    if (threadIdx.x == 0 && blk_e)
+        atomicAdd(&escaped[(blockIdx.x % IM_CNT) * IM_STRIDE], (unsigned long long)blk_e);
+}
+
 }  // namespace
+
+int launch_index_eff16(const agn_log &log, int16_t *eff16, uint64_t *n_esc, hipStream_t st) {
+    *n_esc = 0;
+    if (log.n_entries == 0) return AGN_OK;
+    // eight entries per lane; 8192 blocks hold every CU's waves many times over
+    const uint64_t want = (log.n_entries / 8u + 255u) / 256u;
+    const unsigned nb = (unsigned)(want < 1u ? 1u : want > 8192u ? 8192u : want);
+    unsigned long long *cnt = nullptr;
+    const size_t cb = (size_t)IM_CNT * IM_STRIDE * sizeof(unsigned long long);
+    AGN_HIP(pool_malloc(&cnt, cb, st));
+    if (hipMemsetAsync(cnt, 0, cb, st) != hipSuccess) {
+        (void)hipFreeAsync(cnt, st);
+        return fail(AGN_EHIP, "index_eff16: counter reset");
+    }
+    hipLaunchKernelGGL(k_index_eff16, dim3(nb), dim3(256), 0, st, log.eff, log.n_entries, eff16, cnt);
+    int rc = hipGetLastError() == hipSuccess ? AGN_OK : fail(AGN_EHIP, "index_eff16: launch");
+    // the count is read back here: the call blocks until the tier is built
+    std::vector<unsigned long long> h((size_t)IM_CNT * IM_STRIDE);
+    if (rc == AGN_OK &&
+        (hipMemcpyAsync(h.data(), cnt, cb, hipMemcpyDeviceToHost, st) != hipSuccess ||
+         hipStreamSynchronize(st) != hipSuccess))
+        rc = fail(AGN_EHIP, "index_eff16: escape count");
+    if (rc == AGN_OK)
+        for (uint32_t i = 0; i < IM_CNT; ++i) *n_esc += h[(size_t)i * IM_STRIDE];
+    (void)hipFreeAsync(cnt, st);
+    return rc;
+}
 
 int launch_index_pack16(const agn_log &log, const uint32_t *rows, const uint8_t *ok,
                         uint16_t *rows16, uint8_t *narrow, uint64_t *n_wide, hipStream_t st) {

@@ -175,6 +175,26 @@ class Engine:
         check(self.lib.agn_log_index_pack16(self.ctx, C.byref(ls), None, None, None, None),
               "agn_log_index_pack16")
 
+    def index_eff16(self, dlog, stream=None):
+        """Build and register the effect tier of a device log's packed index
+        (agn_log_index_eff16; index_pack16 first); returns (eff16, n_escaped)
+        -- the buffer is owned by dlog when dlog is DeviceArrays."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        E = int(ls.n_entries)
+        eff16 = self.empty((max(1, E) + 7) // 8 * 16)
+        n = C.c_uint64(0)
+        check(self.lib.agn_log_index_eff16(self.ctx, C.byref(ls), eff16.ptr, C.byref(n), stream),
+              "agn_log_index_eff16")
+        if isinstance(dlog, DeviceArrays):
+            dlog.bufs.update(pack_eff16=eff16)
+        return eff16, n.value
+
+    def drop_eff16(self, dlog):
+        """Drop the effect tier alone (agn_log_index_eff16, eff16 = NULL)."""
+        ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
+        check(self.lib.agn_log_index_eff16(self.ctx, C.byref(ls), None, None, None),
+              "agn_log_index_eff16")
+
     def drop_pack(self, dlog):
         """Drop the log's packed-index registration (agn_log_index_pack, rows = NULL)."""
         ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog

@@ -367,6 +367,34 @@ int agn_log_index_pack(agn_ctx *ctx, const agn_log *log, uint32_t *rows, uint64_
 int agn_log_index_pack16(agn_ctx *ctx, const agn_log *log, uint16_t *rows16, uint8_t *narrow,
                          uint64_t *n_wide, void *stream);
 
+/* The effect tier of the packed index: every entry's effect as an i16, 2 bytes
+ * per op -- a 64-op key's effects are one 128-byte line, loaded with its u16
+ * rows before any verdict, where `eff` is gathered 8 bytes at a time after it.
+ * It serves logs whose effects are small integers (counter increments); a log
+ * of large amounts escapes and keeps the read without the tier.
+ *   eff16[e] ([n_entries] i16) = eff[e] where -32767 <= eff[e] <= 32767, else
+ *     the escape -32768 (0x8000): "read eff[e]".  AGN_EFFECT_INVALID and an
+ *     effect of exactly -32768 escape.  Built for every entry of the log.
+ * The caller owns eff16 (16-byte aligned).  The log must have a registered
+ * narrow tier (agn_log_index_pack16, same key): the tiers nest, u32 index >
+ * narrow tier > effect tier.  The call builds the array, counts the escaped
+ * entries and blocks until it is built; it keeps the count and log->eff, the
+ * array the tier was built from, in the registration and returns the count
+ * through n_escaped (may be NULL).  A read that takes the narrow tier then
+ * loads eff16 in place of eff when its log.eff is the recorded pointer (the
+ * registry key does not include eff) and at most one entry in 1024 escaped;
+ * escaped entries are read from eff.  Results never depend on the tier.
+ * eff16 == NULL drops this tier alone (nothing else is read then), and so does
+ * agn_dev_free of eff16 or of the recorded eff array; dropping or rebuilding
+ * the narrow tier or the u32 index, agn_close and eviction drop it as well.
+ * AGN_ENOTSUP: as agn_log_index_pack16; AGN_EINVAL: no narrow tier registered
+ * for the log, log->eff == NULL, a misaligned eff16.  Environment
+ * AGN_Q2_EFF16=0 keeps reads off the tier, =1 takes it whatever the count of
+ * escaped entries (A/B knob).
+ * An addition to ABI v7: no struct changed, the version number stays. */
+int agn_log_index_eff16(agn_ctx *ctx, const agn_log *log, int16_t *eff16,
+                        uint64_t *n_escaped, void *stream);
+
 /* Upper bound of live pairs per request for set/register types:
  * writes cap_off[n_req+1] (host pointers): cap = #adding entries of the key
  * + #base pairs.  Host-side helper (the bound is static per log): every
