@@ -12,13 +12,14 @@ ABI_VERSION = 7
 OK = 0
 EINVAL, EHIP, ENOMEM, ECAPACITY, ENOTSUP, ERCCL, ENODEV = -1, -2, -3, -4, -5, -6, -7
 
-COUNTER_PN, SET_AW, REGISTER_MV = 1, 2, 3
+COUNTER_PN, SET_AW, REGISTER_MV, REGISTER_LWW = 1, 2, 3, 4
 TYPE_MIXED = 0xFF
 EFFECT_INVALID = -(1 << 63)
 TAG_INVALID = 0xFFFFFFFF
 
 F_NEWSS, F_CT_IGNORE, F_ERR_UNEXPECTED, F_ERR_CORRUPTED, F_ERR_CAPACITY = 0x1, 0x2, 0x4, 0x8, 0x10
 F_CT_FULL = 0x20          # ABI v5: LastOpCt has every column (mask not written)
+F_TS_TIE = 0x40          # register_lww: another candidate has the winner's ts, another tag
 HINT_R_FULL, HINT_CT_FLAG, HINT_MIXED = 0x1, 0x2, 0x4
 OPS_THRESHOLD = 50  # src/materializer_vnode.erl:41
 RESIZE_THRESHOLD = 5  # :44
@@ -30,6 +31,7 @@ TYPE_NAMES = {
     COUNTER_PN: "antidote_crdt_counter_pn",
     SET_AW: "antidote_crdt_set_aw",
     REGISTER_MV: "antidote_crdt_register_mv",
+    REGISTER_LWW: "antidote_crdt_register_lww",
 }
 TYPE_IDS = {v: k for k, v in TYPE_NAMES.items()}
 

@@ -16,11 +16,14 @@ only encodes terms and decodes results.
 from __future__ import annotations
 
 from . import _abi
-from .encode import IGNORE, ClocksiPayload, DcTable, LogEncoder, ReadEncoder, decode_clock
-from .records import (COUNTER_PN, REGISTER_MV, SET_AW, CorruptedOpsCache,
+from .encode import (IGNORE, ClocksiPayload, DcTable, LogEncoder, ReadEncoder, decode_clock,
+                     term_key)
+from .records import (COUNTER_PN, REGISTER_LWW, REGISTER_MV, SET_AW, CorruptedOpsCache,
                       MaterializedSnapshot, SnapshotGetResponse, ops_oldest_first)
 
-_TYPE_IDS = {COUNTER_PN: _abi.COUNTER_PN, SET_AW: _abi.SET_AW, REGISTER_MV: _abi.REGISTER_MV}
+_TYPE_IDS = {COUNTER_PN: _abi.COUNTER_PN, SET_AW: _abi.SET_AW, REGISTER_MV: _abi.REGISTER_MV,
+             REGISTER_LWW: _abi.REGISTER_LWW}
+LWW_NEW = (0, b"")  # antidote_crdt_register_lww:new() = {0, <<>>}
 _engines: dict = {}
 
 
@@ -42,6 +45,8 @@ def type_id(typ: str) -> int:
 def new(typ: str):
     """materializer:create_snapshot/1 = Type:new()."""
     type_id(typ)
+    if typ == REGISTER_LWW:
+        return LWW_NEW
     return 0 if typ == COUNTER_PN else []
 
 
@@ -51,6 +56,8 @@ def value(typ: str, state):
         return state
     if typ == SET_AW:
         return [e for e, _ in state]
+    if typ == REGISTER_LWW:
+        return state[1]
     return [v for v, _ in state]
 
 
@@ -67,11 +74,33 @@ def _base_pairs(typ, snapshot):
         return snapshot
     if typ == SET_AW:
         return [(e, list(toks)) for e, toks in snapshot]
+    if typ == REGISTER_LWW:   # {Ts, Value}: no pair for new(), else (value, ts)
+        ts, v = snapshot
+        return [] if (ts, v) == LWW_NEW else [(v, ts)]
     return [(v, t) for v, t in snapshot]
+
+
+def _lww_values(reads):
+    """Every value a register_lww batch can name (base states and well-formed
+    effects), in Erlang term order: interned in this order, the device's tie
+    break by tag id is update/2's max over the value terms, and the mirror
+    never has to redo an AGN_F_TS_TIE read."""
+    vals = {}
+    for _tx, _r, resp in reads:
+        snap = resp.materialized_snapshot.value
+        if isinstance(snap, tuple) and len(snap) == 2:
+            vals.setdefault(repr(term_key(snap[1])), snap[1])
+        for _i, p in ops_oldest_first(resp.ops_list):
+            e = p.op_param
+            if isinstance(e, tuple) and len(e) == 2:
+                vals.setdefault(repr(term_key(e[1])), e[1])
+    return sorted(vals.values(), key=term_key)
 
 
 def _decode_state(typ, enc, res, i):
     o, n = int(res.out_off[i]), int(res.out_n[i])
+    if typ == REGISTER_LWW:   # out_n == 0: Type:new()
+        return (int(res.out_tok[o]), enc.tags.term(int(res.out_tag[o]))) if n else LWW_NEW
     pairs = [(enc.tags.term(int(t)), enc.tokens.term(int(k)))
              for t, k in zip(res.out_tag[o:o + n], res.out_tok[o:o + n])]
     if typ == SET_AW:
@@ -98,6 +127,9 @@ def materialize_batch(typ: str, reads, device: int = 0):
     D = _n_dcs(resp_clocks)
     enc = LogEncoder(tid, D, dcs=DcTable())
     rd = ReadEncoder(enc, tid)
+    if tid == _abi.REGISTER_LWW:
+        for v in _lww_values(reads):
+            enc.tags.id(v)
     for txid, R, resp in reads:
         k = enc.add_key([(i, ClocksiPayload(p.key, p.type, p.op_param, p.snapshot_time,
                                             p.commit_time, p.txid))

@@ -162,6 +162,10 @@ hipError_t pool_malloc(void **p, size_t bytes, hipStream_t st) {
 }
 
 static bool is_tag_type(uint32_t t) { return t == AGN_SET_AW || t == AGN_REGISTER_MV; }
+// The types whose log entries, base state and result use the tag-type / pair
+// layout: the tag types plus register_lww (tag = value id, tok = timestamp,
+// no removals, at most one pair).
+static bool is_pair_type(uint32_t t) { return is_tag_type(t) || t == AGN_REGISTER_LWW; }
 
 // A log whose key_mask agn_log_index_masks built (same buffer, same key
 // count) with many mixed keys (many_mixed).
@@ -358,7 +362,7 @@ static int validate(const agn_log *log, const agn_read *req, const agn_result *o
     if (misaligned4(log->key_type) || misaligned4(req->sct_ignore))
         return fail(AGN_EINVAL, "key_type / sct_ignore must be 4-byte aligned");
     if (log->n_dcs == 0 || log->n_dcs > 256) return fail(AGN_EINVAL, "n_dcs=%u not in [1,256]", log->n_dcs);
-    if (log->crdt_type != AGN_COUNTER_PN && !is_tag_type(log->crdt_type))
+    if (log->crdt_type != AGN_COUNTER_PN && !is_pair_type(log->crdt_type))
         return fail(AGN_EINVAL, "unknown crdt_type %u", log->crdt_type);
     if (req->n_req == 0) return AGN_OK;
     if (!log->key_off) return fail(AGN_EINVAL, "log: key_off required");
@@ -372,6 +376,12 @@ static int validate(const agn_log *log, const agn_read *req, const agn_result *o
     if (log->crdt_type == AGN_COUNTER_PN) {
         if (log->n_entries && !log->eff) return fail(AGN_EINVAL, "counter_pn log needs eff");
         if (!out->value) return fail(AGN_EINVAL, "counter_pn result needs value");
+    } else if (log->crdt_type == AGN_REGISTER_LWW) {
+        // no removals: rem_off / rem_tok are not read for the type
+        if (log->n_entries && (!log->tag || !log->add_tok))
+            return fail(AGN_EINVAL, "register_lww log needs tag/add_tok");
+        if (!out->out_off || !out->out_n || !out->out_tag || !out->out_tok)
+            return fail(AGN_EINVAL, "register_lww result needs out_off/out_n/out_tag/out_tok");
     } else {
         if (log->n_entries && (!log->tag || !log->add_tok || !log->rem_off))
             return fail(AGN_EINVAL, "set/register log needs tag/add_tok/rem_off");
@@ -692,6 +702,17 @@ int agn_state_capacity(const agn_log *log, const agn_read *req, uint64_t *cap_of
     for (uint64_t i = 0; i < req->n_req; ++i) {
         const uint64_t k = req->keys ? req->keys[i] : i;
         uint64_t c = 0;
+        if (log->crdt_type == AGN_REGISTER_LWW) {
+            // one pair at most: the key has an entry or the request a base pair
+            const uint64_t b = req->base_off     ? req->base_off[i + 1] - req->base_off[i]
+                               : req->base_value ? AGN_SS_STATE_PAIRS(req->base_value[i])
+                                                 : 0;
+            if (b > 1)
+                return fail(AGN_EINVAL, "register_lww: request %llu has %llu base pairs",
+                            (unsigned long long)i, (unsigned long long)b);
+            cap_off[i + 1] = cap_off[i] + ((b || key_n(log->key_off, log->key_len, k)) ? 1 : 0);
+            continue;
+        }
         if (log->add_tok)
             for (uint64_t e = log->key_off[k]; e < log->key_off[k] + key_n(log->key_off, log->key_len, k); ++e)
                 c += log->add_tok[e] != 0;
@@ -789,6 +810,13 @@ extern "C" {
 int agn_materialize_host(agn_ctx *ctx, const agn_log *log, const agn_read *req, agn_result *out) {
     int rc = validate(log, req, out);
     if (rc) return rc;
+    // host arrays: the one thing validate() cannot see in device memory
+    if (log->crdt_type == AGN_REGISTER_LWW && (req->base_off || req->base_value))
+        for (uint64_t i = 0; i < req->n_req; ++i)
+            if ((req->base_off ? req->base_off[i + 1] - req->base_off[i]
+                               : AGN_SS_STATE_PAIRS(req->base_value[i])) > 1)
+                return fail(AGN_EINVAL, "register_lww: request %llu has more than one base pair",
+                            (unsigned long long)i);
     rc = use_device(ctx);
     if (rc) return rc;
     if (req->n_req == 0) return AGN_OK;
@@ -798,7 +826,7 @@ int agn_materialize_host(agn_ctx *ctx, const agn_log *log, const agn_read *req, 
     if (log->rem_off && log->key_len)  // segmented log: the token arena's high-water mark
         for (uint64_t e = 0; e <= E; ++e) n_rem = std::max<uint64_t>(n_rem, log->rem_off[e]);
     uint64_t n_base = req->base_off ? req->base_off[Q] : 0;
-    if (!req->base_off && req->base_value && is_tag_type(log->crdt_type))  // arena references
+    if (!req->base_off && req->base_value && is_pair_type(log->crdt_type))  // arena references
         for (uint64_t i = 0; i < Q; ++i)
             n_base = std::max<uint64_t>(n_base, AGN_SS_STATE_START(req->base_value[i]) +
                                                     AGN_SS_STATE_PAIRS(req->base_value[i]));
@@ -951,7 +979,7 @@ int agn_log_ingest(agn_ctx *ctx, const agn_log_records *recs, uint32_t crdt_type
                    uint64_t *out_totals, void *stream) {
     if (!recs || !out) return fail(AGN_EINVAL, "log_ingest: null descriptor");
     if (n_dcs == 0 || n_dcs > 256) return fail(AGN_EINVAL, "log_ingest: n_dcs=%u", n_dcs);
-    if (crdt_type != AGN_COUNTER_PN && !is_tag_type(crdt_type))
+    if (crdt_type != AGN_COUNTER_PN && !is_pair_type(crdt_type))
         return fail(AGN_EINVAL, "log_ingest: crdt_type %u", crdt_type);
     if (n_keys >= (1ull << 24)) return fail(AGN_ENOTSUP, "log_ingest: n_keys >= 2^24");
     if (recs->n >= 0x7fffffffull) return fail(AGN_ENOTSUP, "log_ingest: n >= 2^31 records");
@@ -1029,7 +1057,7 @@ int agn_ss_store(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint64_t
         return fail(AGN_EINVAL, "ss_store: null argument");
     if (log->n_keys != cache->n_keys || log->n_dcs != cache->n_dcs)
         return fail(AGN_EINVAL, "ss_store: log and cache disagree on keys / DCs");
-    const bool arena = cache->state_tag != nullptr && is_tag_type(log->crdt_type);
+    const bool arena = cache->state_tag != nullptr && is_pair_type(log->crdt_type);
     if (n_req && (!is_first || !status || !res->hole || !res->lastct || !res->count ||
                   !res->flags || (!arena && !handle && !res->value) ||
                   (arena && (!res->out_off || !res->out_n || !res->out_tag || !res->out_tok))))
@@ -1175,7 +1203,7 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
     if (!log || !out || !log->key_off) return fail(AGN_EINVAL, "read_cached: null argument");
     if (log->n_keys != cache->n_keys || log->n_dcs != cache->n_dcs)
         return fail(AGN_EINVAL, "read_cached: log and cache disagree on keys / DCs");
-    if (is_tag_type(log->crdt_type)) {
+    if (is_pair_type(log->crdt_type)) {
         if (!cache->state_tag || !cache->state_tok || !cache->state_ctl || cache->clock_mask)
             return fail(AGN_ENOTSUP, "read_cached: set/register needs a cache with a state "
                                      "arena and dense clocks");
@@ -1383,7 +1411,7 @@ int check_cfg(const agn_gen_cfg *c) {
     if (!c) return fail(AGN_EINVAL, "null cfg");
     if (c->n_dcs == 0 || c->n_dcs > 256) return fail(AGN_EINVAL, "gen: n_dcs");
     if (c->ops_per_key >= (1u << 24) - 1) return fail(AGN_EINVAL, "gen: ops_per_key");
-    if (c->crdt_type != AGN_COUNTER_PN && !is_tag_type(c->crdt_type))
+    if (c->crdt_type != AGN_COUNTER_PN && !is_pair_type(c->crdt_type))
         return fail(AGN_EINVAL, "gen: crdt_type");
     return AGN_OK;
 }
@@ -1451,6 +1479,7 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
     const uint32_t D = c.n_dcs;
     const uint64_t K = c.n_keys, E = K * c.ops_per_key;
     const bool tags = is_tag_type(c.crdt_type);
+    const bool pairs = is_pair_type(c.crdt_type);  // + register_lww: the arrays, no removals
     int err = AGN_OK;
     log->crdt_type = c.crdt_type;
     log->n_dcs = D;
@@ -1459,7 +1488,7 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
     log->key_off = dmalloc<uint64_t>(K + 1, err);
     log->oc = dmalloc<uint64_t>(E * D, err);
     log->op_id = dmalloc<uint32_t>(E, err);
-    if (!tags) {
+    if (!pairs) {
         log->eff = dmalloc<int64_t>(E, err);
     } else {
         log->tag = dmalloc<uint32_t>(E, err);
@@ -1500,6 +1529,9 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
     } else if (tags) {
         (void)hipMemsetAsync((void *)log->rem_off, 0, sizeof(uint32_t), s);
         log->rem_tok = dmalloc<uint64_t>(1, err);
+    } else if (pairs) {  // register_lww: every removal range is empty
+        (void)hipMemsetAsync((void *)log->rem_off, 0, (E + 1) * sizeof(uint32_t), s);
+        log->rem_tok = dmalloc<uint64_t>(1, err);
     }
     if (err) { (void)hipFree(scratch); agn_gen_free_dev(ctx, log, req); return err; }
     if (K == 0) (void)hipMemsetAsync((void *)log->key_off, 0, sizeof(uint64_t), s);
@@ -1510,7 +1542,7 @@ int agn_gen_dev(agn_ctx *ctx, const agn_gen_cfg *cfg, agn_log *log, agn_read *re
     if (!err && he == hipSuccess && K) err = launch_index_ids(*log, (uint32_t *)log->key_id0, s);
     // and the packed index of a counter_pn D = 8 log (agn_log_index_pack), owned
     // by the context; a failed allocation leaves the log without one
-    if (!err && he == hipSuccess && !tags && D == 8 && E) {
+    if (!err && he == hipSuccess && !pairs && D == 8 && E) {
         void *pr = nullptr, *pb = nullptr, *po = nullptr;
         if (hipMalloc(&pr, E * 8 * sizeof(uint32_t)) == hipSuccess &&
             hipMalloc(&pb, K * 8 * sizeof(uint64_t)) == hipSuccess &&
@@ -1595,6 +1627,7 @@ int agn_gen_host(const agn_gen_cfg *cfg, agn_log *log, agn_read *req) {
     const uint32_t D = c.n_dcs, N = c.ops_per_key;
     const uint64_t K = c.n_keys, E = K * N;
     const bool tags = is_tag_type(c.crdt_type);
+    const bool pairs = is_pair_type(c.crdt_type);  // + register_lww: the arrays, no removals
     auto hm = [](uint64_t bytes) { return std::calloc(bytes ? bytes : 1, 1); };
     log->crdt_type = c.crdt_type;
     log->n_dcs = D;
@@ -1605,7 +1638,7 @@ int agn_gen_host(const agn_gen_cfg *cfg, agn_log *log, agn_read *req) {
     log->key_off = key_off;
     log->oc = (uint64_t *)hm(E * D * 8);
     log->op_id = (uint32_t *)hm(E * 4);
-    if (!tags) log->eff = (int64_t *)hm(E * 8);
+    if (!pairs) log->eff = (int64_t *)hm(E * 8);
     else {
         log->tag = (uint32_t *)hm(E * 4);
         log->add_tok = (uint64_t *)hm(E * 8);
@@ -1660,6 +1693,8 @@ int agn_gen_host(const agn_gen_cfg *cfg, agn_log *log, agn_read *req) {
         ro[0] = 0;
         for (uint64_t e = 0; e < E; ++e) ro[e + 1] += ro[e];
         log->rem_tok = (uint64_t *)hm((uint64_t)ro[E] * 8);
+    } else if (pairs) {
+        log->rem_tok = (uint64_t *)hm(0);  // rem_off stays all zero
     }
     par(1);
     return AGN_OK;

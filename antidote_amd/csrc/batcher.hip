@@ -530,6 +530,7 @@ int run_batch_cached_tags(agn_batcher *B, std::vector<Pending *> &b) {
         agn_log v;  // the shape only (the log's view is taken under its hold)
         std::memset(&v, 0, sizeof v);
         v.n_dcs = D;
+        v.crdt_type = B->crdt;
         if (tags_serve_supported(v, sparse)) return run_batch_tags_fused(B, b, sparse);
     }
     std::vector<uint64_t> keys(n);

@@ -347,6 +347,7 @@ int tune_counter_dense(const agn_log &log, const agn_read &req, const agn_result
                        hipStream_t st, int rounds, int *choice, float *ms);
 int launch_tags(const agn_log &log, const agn_read &req, const agn_result &out,
                 hipStream_t s);
+int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t s);
 int launch_gst_min(uint32_t D, uint64_t P, uint64_t E, const uint64_t *clocks,
                    const uint8_t *defined, uint64_t *out, hipStream_t s);
 int launch_gst_finalize(uint32_t D, uint64_t E, uint64_t *vec, hipStream_t s);

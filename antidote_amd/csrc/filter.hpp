@@ -174,7 +174,9 @@ struct KeyFilter {
             if (writer) out.lastct[i * D + (uint32_t)c] = (m && !ct_ign) ? m - 1ull : 0ull;
             if (SPARSE && out.lastct_mask != nullptr) {
                 const uint64_t pm = ballot(writer && m != 0ull && !ct_ign);
-                if (lane == 0) out.lastct_mask[i * W + (uint32_t)t] = pm;
+                // (D in 129..192: T = 4 column groups but W = 3 mask words)
+                if (lane == 0 && (S::T == 1 || (uint32_t)t < W))
+                    out.lastct_mask[i * W + (uint32_t)t] = pm;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

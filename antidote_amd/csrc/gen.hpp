@@ -16,6 +16,8 @@
 //         register_mv: value U[0,E-1]; U[0,99] < 5 -> reset(live tokens);
 //                      else assign a fresh token overriding the live tokens
 //                      unless concurrent (U[0,99] < 20 and < 4 live)
+//         register_lww: value U[0,E-1]; timestamp clk[c] (the op's commit
+//                      time) + U[0,15]
 //   R[d]   = max(clk0[d], oc[d] of ops < cut) + U[0,4000] - J, J = min(2000, 16000/D)
 //            (J shrinks with D so that wide clocks still include a prefix-ish
 //            subset: every one of the op's D entries must be <= R)
@@ -112,6 +114,17 @@ AGN_HD inline void gen_key(const agn_gen_cfg &cfg, uint64_t k, GenOut &o) {
         if (cfg.crdt_type == AGN_COUNTER_PN) {
             const int64_t eff = (int64_t)rng.uni(0, 2000) - 1000;
             if (write) o.eff[i] = eff;
+            continue;
+        }
+        if (cfg.crdt_type == AGN_REGISTER_LWW) {
+            // its own draws, after the op's clock draws: the other types'
+            // streams are untouched
+            const uint32_t val = (uint32_t)rng.uni(0, E - 1);
+            const uint64_t ts = o.clk[c] + rng.uni(0, 15);
+            if (write) {
+                o.tag[i] = val;
+                o.add_tok[i] = ts;
+            }
             continue;
         }
         const uint64_t tok = (gk << 24) | (uint64_t)(i + 1);

@@ -1,0 +1,214 @@
+// mat_lww.hip — batched clocksi_materializer:materialize/4 for
+// antidote_crdt_register_lww on gfx950 (one wave per key, grid-stride).
+//
+// Reference: materialize/4 src/clocksi_materializer.erl:89-101,
+// apply_operations :113-121 with register_lww update(Effect, State) =
+// max(Effect, State) over {Ts, Value} (antidote_crdt 0.1.2, restated in
+// SURVEY.md §8(a) a5.4; parity-unpinned beyond the sequential assign).  The
+// snapshot filter is filter.hpp, the bookkeeping (NewLastOp, Count, LastOpCt,
+// the error position) that of mat_counter.hip.
+//   state = max by (ts, tag), unsigned and lexicographic, over the base pair
+//           (if any) and every included entry whose tag is valid
+//   AGN_F_TS_TIE: another candidate carries the winner's ts under another tag
+//           (tag ids are interner ids, not Erlang term order)
+// Every lane keeps the best (ts, tag) of the included ops it saw plus a "tied
+// at my best ts" bit; the wave then reduces in two steps, the u64 maximum of
+// ts and the u32 maximum of tag among the lanes at that ts, and the tie ballot
+// is the lanes at that ts whose tag differs or whose own bit is set.
+//
+// ts / tag loads: a chunk's ts and tag do not depend on its verdict.  EARLY
+// issues them with the chunk's rows for every valid op (8*D + 12 bytes per op);
+// the late form loads them for the included ops only, after the verdict (8*D
+// bytes per op + 12 per included op, one more dependent round trip per chunk).
+// The default is the early form: cfg2's shape (10M keys x 64 ops, D = 8, cold,
+// 32 % included) 15.90 ms against 16.04 ms late and 14.32 ms for k_counter at
+// 8*D + 8 (scripts/ab_lww.py); AGN_LWW_LOAD=late selects the
+// other (A/B knob).
+// Per key: 16 (key_off pair) + 8*D (R) + 8*D (LastOpCt) + 20 (hole, count,
+// flags, err_pos) + 16 (out_off pair) + 4 (out_n) + 12 (the pair).
+#include <cstdlib>
+
+#include "filter.hpp"
+
+namespace agn {
+namespace {
+
+// One more candidate into a lane's running maximum.
+__device__ __forceinline__ void lww_take(bool c, uint64_t ts, uint32_t tag, bool &have,
+                                         uint64_t &bts, uint32_t &btag, bool &tie) {
+    if (!c) return;
+    if (!have || ts > bts) {
+        bts = ts;
+        btag = tag;
+        tie = false;
+    } else if (ts == bts && tag != btag) {
+        tie = true;
+        btag = tag > btag ? tag : btag;
+    }
+    have = true;
+}
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, AGN_WAVE);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = umax64(v, shfl_xor_u64(v, m));
+    return v;
+}
+
+// The one-lane-per-op shapes are held to k_counter's five waves per SIMD (96
+// VGPRs; left alone the kernel takes 100 and runs four).
+template <int DPL, int LPO, bool SPARSE, bool EARLY>
+__global__ __launch_bounds__(256, (LPO == 1 ? 5 : 1)) void k_lww(agn_log log, agn_read req,
+                                                                 agn_result out) {
+    using F = KeyFilter<DPL, LPO, SPARSE>;
+    __shared__ uint64_t stage[4][DPL][AGN_WAVE];
+    const int w = threadIdx.x >> 6;
+    const uint64_t nw = (uint64_t)gridDim.x * 4u;
+
+    for (uint64_t i = (uint64_t)blockIdx.x * 4u + (uint64_t)w; i < req.n_req; i += nw) {
+        const uint64_t key = req.keys ? uniform_u64(req.keys[i]) : i;
+        const uint64_t off = uniform_u64(log.key_off[key]);
+        const uint64_t n = uniform_u64(key_n(log.key_off, log.key_len, key));
+        const int lane = lane_id();
+
+        if (n != 0 && log.key_type != nullptr && log.key_type[key] != (uint8_t)req.req_type) {
+            if (lane == 0) {  // erlang:error(corrupted_ops_cache) (:190-191)
+                out.flags[i] = AGN_F_ERR_CORRUPTED;
+                out.err_pos[i] = 0xffffffffu;
+                out.out_n[i] = 0;
+            }
+            continue;
+        }
+
+        F f;
+        f.init(log, req, i);
+        bool have = false, tie = false;
+        uint64_t bts = 0;
+        uint32_t btag = 0;
+        uint32_t cnt = 0;
+        int64_t first_err = -1;
+        for (uint64_t b = 0; b < n; b += F::S::OPI) {
+            const uint64_t e = off + b + (uint64_t)f.slot;
+            uint64_t ts = 0;
+            uint32_t tg = AGN_TAG_INVALID;
+            if (EARLY && f.sub == 0 && b + (uint64_t)f.slot < n) {
+                ts = log.add_tok[e];
+                tg = log.tag[e];
+            }
+            bool valid;
+            const bool incl = f.step(log, off, n, b, valid);
+            const bool lead = incl && f.sub == 0;
+            if (!EARLY && lead) {
+                ts = log.add_tok[e];
+                tg = log.tag[e];
+            }
+            const bool bad = lead && tg == AGN_TAG_INVALID;
+            cnt += (uint32_t)__builtin_popcountll(ballot(lead));
+            if (first_err < 0) {
+                const uint64_t be = ballot(bad);
+                if (be) first_err = (int64_t)b + (int64_t)(__builtin_ctzll(be) / LPO);
+            }
+            lww_take(lead && !bad, ts, tg, have, bts, btag, tie);
+        }
+
+        // the base state: at most one pair (the first of more), through the
+        // CSR or an AGN_SS_STATE(start, pairs) reference in base_value
+        if (lane == 0 && req.base_tag != nullptr && req.base_tok != nullptr) {
+            uint64_t b0 = 0;
+            uint32_t B = 0;
+            if (req.base_off) {
+                b0 = req.base_off[i];
+                B = (uint32_t)(req.base_off[i + 1] - b0);
+            } else if (req.base_value) {
+                const uint64_t ref = (uint64_t)req.base_value[i];
+                b0 = AGN_SS_STATE_START(ref);
+                B = AGN_SS_STATE_PAIRS(ref);
+            }
+            if (B != 0u) lww_take(true, req.base_tok[b0], req.base_tag[b0], have, bts, btag, tie);
+        }
+
+        const bool any = ballot(have) != 0ull;
+        const uint64_t wts = wave_max_u64(have ? bts : 0ull);
+        const bool at = have && bts == wts;
+        const uint32_t wtag = wave_max_u32(at ? btag : 0u);
+        const bool tied = ballot(at && (tie || btag != wtag)) != 0ull;
+
+        const bool ct_ign = f.sct_ign && cnt == 0u;
+        f.write_ct(stage[w], out, i, ct_ign);
+
+        if (lane == 0) {
+            int64_t hole;
+            if (f.first_excl >= 0) hole = (int64_t)log.op_id[off + (uint64_t)f.first_excl] - 1;
+            else hole = n ? (int64_t)log.op_id[off + n - 1] : 0;
+            uint32_t fl = 0;
+            if (cnt) fl |= AGN_F_NEWSS;
+            if (ct_ign) fl |= AGN_F_CT_IGNORE;
+            uint32_t n_live = 0;
+            if (first_err >= 0) {
+                fl |= AGN_F_ERR_UNEXPECTED;
+            } else if (any) {
+                n_live = 1;
+                if (tied) fl |= AGN_F_TS_TIE;
+                const uint64_t o = out.out_off[i];
+                if (out.out_off[i + 1] - o == 0ull) {
+                    fl |= AGN_F_ERR_CAPACITY;
+                } else {
+                    out.out_tag[o] = wtag;
+                    out.out_tok[o] = wts;
+                }
+            }
+            out.hole[i] = hole;
+            out.count[i] = cnt;
+            out.flags[i] = fl;
+            out.err_pos[i] =
+                first_err >= 0 ? (uint32_t)(off + (uint64_t)first_err) : 0xffffffffu;
+            out.out_n[i] = n_live;
+        }
+    }
+}
+
+template <int DPL, int LPO, bool SPARSE, bool EARLY>
+int launch_shape(const agn_log &log, const agn_read &req, const agn_result &out,
+                 hipStream_t st) {
+    const unsigned blocks = grid_for(req.n_req, 4, 0x7fffffffu);  // one wave per request
+    hipLaunchKernelGGL((k_lww<DPL, LPO, SPARSE, EARLY>), dim3(blocks), dim3(256), 0, st, log,
+                       req, out);
+    AGN_HIP(hipGetLastError());
+    return AGN_OK;
+}
+
+template <bool SPARSE, bool EARLY>
+int dispatch(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t st) {
+#define AGN_L(DPL, LPO) launch_shape<DPL, LPO, SPARSE, EARLY>(log, req, out, st)
+    AGN_DISPATCH_SHAPES(log.n_dcs, AGN_L)
+#undef AGN_L
+}
+
+}  // namespace
+
+int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t st) {
+    if (req.n_req == 0) return AGN_OK;
+    // base_value without base_off names AGN_SS_STATE references into
+    // base_tag / base_tok: both arrays are required for them
+    if (!req.base_off && req.base_value && (!req.base_tag || !req.base_tok))
+        return fail(AGN_EINVAL, "register_lww read: base_value (state references) without base_tag/base_tok");
+    // AGN_LWW_LOAD=late loads ts / tag after the verdict (A/B)
+    const bool late = [] {
+        const char *v = AGN_KNOB("AGN_LWW_LOAD");
+        return v && v[0] == 'l';
+    }();
+    const bool sparse = log.oc_mask || req.R_mask || req.sct_mask || out.lastct_mask;
+    if (late) return sparse ? dispatch<true, false>(log, req, out, st)
+                            : dispatch<false, false>(log, req, out, st);
+    return sparse ? dispatch<true, true>(log, req, out, st) : dispatch<false, true>(log, req, out, st);
+}
+
+}  // namespace agn

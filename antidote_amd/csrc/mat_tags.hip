@@ -1033,6 +1033,7 @@ int serve_dispatch(const agn_log &log, const agn_read &req, const agn_result &ou
 // AGN_TAGS_CT=0); odd D with the per-entry-mask or non-FULL dense rows;
 // D = 16, 32, 64 in the CT form (4 DCs per lane), dense or MSK
 bool tags_serve_supported(const agn_log &log, bool sparse) {
+    if (log.crdt_type == AGN_REGISTER_LWW) return false;  // k_lww: the batcher's sequence path
     const uint32_t D = log.n_dcs;
     if (D == 16 || D == 32 || D == 64) {  // the CT shapes, dense or MSK
         if (!tags_ct()) return false;
@@ -1072,6 +1073,7 @@ int launch_tags_serve_rest(const agn_log &log, const agn_read &req, const agn_re
 
 int launch_tags(const agn_log &log, const agn_read &req, const agn_result &out,
                 hipStream_t st) {
+    if (log.crdt_type == AGN_REGISTER_LWW) return launch_lww(log, req, out, st);
     if (req.n_req == 0) return AGN_OK;
     // base_value without base_off names AGN_SS_STATE references into
     // base_tag / base_tok (ABI v4): both arrays are required for them

@@ -60,6 +60,25 @@ class Interner:
         return len(self._terms)
 
 
+def term_key(t):
+    """A sort key in Erlang term order for the terms this package models:
+    number < atom (str, bool) < tuple (by size, then elementwise) < list
+    (elementwise) < binary (bytes); anything else last, by repr."""
+    if isinstance(t, bool):
+        return (1, "true" if t else "false")
+    if isinstance(t, (int, float)):
+        return (0, t)
+    if isinstance(t, str):
+        return (1, t)
+    if isinstance(t, tuple):
+        return (4, len(t), [term_key(x) for x in t])
+    if isinstance(t, list):
+        return (6, [term_key(x) for x in t])
+    if isinstance(t, (bytes, bytearray)):
+        return (7, bytes(t))
+    return (8, repr(t))
+
+
 class DcTable(Interner):
     """dcid() -> column index."""
 
@@ -171,6 +190,17 @@ class LogEncoder:
                 value, token, ovr = effect
                 return [(self.tags.id(value), self.tokens.id(token),
                          [self.tokens.id(x) for x in ovr])]
+            if t == _abi.REGISTER_LWW:
+                # {Ts, Value}: the timestamp goes into add_tok raw (the fold
+                # compares it), not through the token interner.  downstream/2
+                # gives Ts >= 1; anything else (Ts = 0 included: a deviation,
+                # DESIGN.md) is an invalid entry
+                if not (isinstance(effect, tuple) and len(effect) == 2):
+                    return None
+                ts, value = effect
+                if not isinstance(ts, int) or isinstance(ts, bool) or not (1 <= ts <= _abi.U64_MAX):
+                    return None
+                return [(self.tags.id(value), ts, [])]
         except (TypeError, ValueError):
             return None
         return None
@@ -307,6 +337,10 @@ class ReadEncoder:
                 T[i] = e.txids.id(txid)
             if e.crdt_type == _abi.COUNTER_PN:
                 BV[i] = 0 if base is None else int(base)
+            elif e.crdt_type == _abi.REGISTER_LWW:
+                for value_term, ts in (base or []):   # 0 or 1 pair: tok = the raw timestamp
+                    btag.append(e.tags.id(value_term))
+                    btok.append(int(ts))
             else:
                 for tag_term, toks in (base or []):
                     for tk in (toks if e.crdt_type == _abi.SET_AW else [toks]):
@@ -319,11 +353,18 @@ class ReadEncoder:
 
 
 def state_capacity(log: EncodedLog, req: EncodedRead) -> np.ndarray:
-    """Upper bound of live pairs per request (adding entries + base pairs)."""
+    """Upper bound of live pairs per request (adding entries + base pairs);
+    register_lww: 1 where the key has an entry or the request a base pair."""
     adds = (log.add_tok != 0).astype(np.uint64) if log.add_tok is not None else None
     cap = np.zeros(req.n_req + 1, np.uint64)
     for i, k in enumerate(req.keys):
         a, b = int(log.key_off[k]), int(log.key_off[k + 1])
+        if log.crdt_type == _abi.REGISTER_LWW:
+            nb = int(req.base_off[i + 1] - req.base_off[i])
+            if nb > 1:
+                raise ValueError(f"register_lww: request {i} has {nb} base pairs")
+            cap[i + 1] = cap[i] + (1 if (b > a or nb) else 0)
+            continue
         c = int(adds[a:b].sum()) if adds is not None else 0
         c += int(req.base_off[i + 1] - req.base_off[i])
         cap[i + 1] = cap[i] + c

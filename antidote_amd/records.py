@@ -9,6 +9,7 @@ from .encode import IGNORE, ClocksiPayload  # noqa: F401  (#clocksi_payload{}, :
 COUNTER_PN = "antidote_crdt_counter_pn"
 SET_AW = "antidote_crdt_set_aw"
 REGISTER_MV = "antidote_crdt_register_mv"
+REGISTER_LWW = "antidote_crdt_register_lww"
 FIRST_OP = 4  # include/antidote.hrl:90
 
 

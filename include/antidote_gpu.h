@@ -60,12 +60,13 @@ extern "C" {
 #define AGN_COUNTER_PN 1   /* antidote_crdt_counter_pn */
 #define AGN_SET_AW 2       /* antidote_crdt_set_aw     */
 #define AGN_REGISTER_MV 3  /* antidote_crdt_register_mv */
+#define AGN_REGISTER_LWW 4 /* antidote_crdt_register_lww (addition to ABI v7) */
 #define AGN_TYPE_MIXED 0xFF /* key_type marker: the key's ops have different types */
 
 /* counter_pn effect that the Erlang side could not encode as an i64: applying
  * it yields {error,{unexpected_operation,Op,Type}} (src/materializer.erl:53-58) */
 #define AGN_EFFECT_INVALID INT64_MIN
-/* set_aw / register_mv entry whose effect could not be encoded */
+/* set_aw / register_mv / register_lww entry whose effect could not be encoded */
 #define AGN_TAG_INVALID 0xFFFFFFFFu
 
 /* ---- per-key result flags --------------------------------------------- */
@@ -87,6 +88,12 @@ extern "C" {
  * DCs); set only for requests of a batch with AGN_HINT_CT_FLAG, and then
  * lastct_mask[i] is NOT written (the mask is the n_dcs low bits) */
 #define AGN_F_CT_FULL 0x20u
+/* register_lww (addition to ABI v7): some other candidate of the fold (base
+ * pair or included entry) carries the winner's timestamp under a different
+ * tag.  The device breaks the tie by the larger tag id; tag ids are interner
+ * ids, not Erlang term order, so a binding that sees the flag can redo that
+ * one read on the host (or intern its values in term order). */
+#define AGN_F_TS_TIE 0x40u
 
 /* ---- value domain ------------------------------------------------------
  * What agn_log / agn_read fields may hold; every kernel is tested bit-exact
@@ -106,6 +113,12 @@ extern "C" {
  *   add_tok / rem_tok / base_tok: any non-zero u64, 2^64 - 1 included; 0 in
  *     add_tok means "none" (a remove / reset entry).
  *   tag / base_tag: any u32 but 0xFFFFFFFF (AGN_TAG_INVALID, reserved).
+ *   register_lww: tag[e] is the interned value id (any u32 but
+ *     AGN_TAG_INVALID, which marks an effect the encoder could not
+ *     represent); add_tok[e] is the effect's timestamp, ANY u64 (0 and
+ *     2^64 - 1 included), compared unsigned.  In a base / result pair `tag` is
+ *     the value id and `tok` the timestamp.  (A host encoder maps an effect
+ *     that is not {integer Ts, V} with 1 <= Ts < 2^64 to an invalid entry.)
  *   op_id: any u32 but 0xFFFFFFFF (AGN_ID0_NONE, reserved by the id index);
  *     `hole` is the id zero-extended to int64, or id - 1.
  *   txid: any non-zero u64, 2^64 - 1 included; 0 means "none" in the log and
@@ -113,7 +126,7 @@ extern "C" {
 
 /* ---- op log (device or host pointers, same layout) -------------------- */
 typedef struct agn_log {
-    uint32_t crdt_type;       /* AGN_COUNTER_PN / AGN_SET_AW / AGN_REGISTER_MV */
+    uint32_t crdt_type;       /* AGN_COUNTER_PN / AGN_SET_AW / AGN_REGISTER_MV / AGN_REGISTER_LWW */
     uint32_t n_dcs;           /* D: vector-clock width */
     uint64_t n_keys;
     uint64_t n_entries;
@@ -134,6 +147,19 @@ typedef struct agn_log {
     const uint32_t *rem_off;  /* [n_entries+1] CSR into rem_tok (with key_len: contiguous
                                  within a key, rem_off[key_off[k]+key_len[k]] = end) */
     const uint64_t *rem_tok;  /* removed (set) / overridden (register) tokens */
+    /* AGN_REGISTER_LWW: entry = {Ts, Value} in the tag-type arrays: tag = value
+     * id, add_tok = Ts.  agn_materialize does not read rem_off / rem_tok for
+     * the type (they may be NULL there); in the engine-owned op log and for
+     * agn_prune_ops / agn_log_ingest an entry is a tag-type entry whose removal
+     * range is empty.  The base state and the result use the pair layout with
+     * 0 or 1 pair per request (two or more base pairs: AGN_EINVAL where the
+     * host sees them, on the device the first is used); out_n == 0 means
+     * Type:new().  Fold: the maximum by (ts, tag), unsigned and lexicographic,
+     * over the base pair and every included entry whose tag is valid;
+     * AGN_F_TS_TIE as defined above; an included entry with AGN_TAG_INVALID
+     * gives AGN_F_ERR_UNEXPECTED with err_pos the oldest such entry (out_n and
+     * the pair are then unspecified); one live pair and no room gives
+     * AGN_F_ERR_CAPACITY with out_n = 1. */
     /* ABI v3, optional (NULL = read op_id): per key, the op id of the segment's
      * first entry when its ids are consecutive (op_id[off+p] == key_id0 + p
      * for every p < len), else AGN_ID0_NONE.  Ids stay consecutive from
@@ -401,7 +427,9 @@ int agn_log_index_eff16(agn_ctx *ctx, const agn_log *log, int16_t *eff16,
  * array of host_log / host_req it reads -- key_off / key_len, the adding
  * flags, base_off, or base_value's AGN_SS_STATE references when base_off is
  * NULL -- must be host memory (copy a device agn_ss_lookup's base_value
- * back first). */
+ * back first).  AGN_REGISTER_LWW: cap = 1 where the key has an entry or the
+ * request a base pair, else 0; a request with two or more base pairs is
+ * AGN_EINVAL. */
 int agn_state_capacity(const agn_log *host_log, const agn_read *host_req,
                        uint64_t *cap_off);
 
@@ -442,7 +470,7 @@ int agn_oplog_destroy(agn_oplog *log);
  * agn_ss_store(should_gc) + agn_oplog_prune) when it sees the flag.  oc[n][D] is the
  * OpSSCommit row (+ oc_mask[n][W] for a sparse log), txid may be NULL, the
  * effect arrays are those of the log's type, rem_off[n+1] is a CSR into
- * rem_tok. */
+ * rem_tok (AGN_REGISTER_LWW: rem_off may be NULL, every range empty). */
 int agn_oplog_append(agn_oplog *log, uint64_t n, const uint64_t *keys, const uint8_t *same_op,
                      const uint64_t *oc, const uint64_t *oc_mask, const uint64_t *txid,
                      const int64_t *eff, const uint32_t *tag, const uint64_t *add_tok,
