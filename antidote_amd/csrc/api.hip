@@ -1271,6 +1271,19 @@ int agn_prune_ops(agn_ctx *ctx, const agn_log *log, const uint8_t *prune,
         return fail(AGN_EINVAL, "prune_ops: key_off / threshold required");
     if (log->n_entries && (!log->oc || !log->op_id || !out->oc || !out->op_id))
         return fail(AGN_EINVAL, "prune_ops: oc / op_id required");
+    // The kernels pick the entry layout from rem_off alone; a log with entries
+    // must carry its type's arrays, in the CSR and in the segmented form alike.
+    if (log->n_entries) {
+        if (is_pair_type(log->crdt_type)) {
+            if (!log->tag || !log->add_tok || !log->rem_off)
+                return fail(AGN_EINVAL, "prune_ops: crdt_type %u needs tag / add_tok / rem_off",
+                            log->crdt_type);
+        } else if (log->crdt_type == AGN_COUNTER_PN) {
+            if (!log->eff) return fail(AGN_EINVAL, "prune_ops: counter_pn needs eff");
+        } else {
+            return fail(AGN_EINVAL, "prune_ops: unknown crdt_type %u", log->crdt_type);
+        }
+    }
     if ((log->oc_mask && !out->oc_mask) || (log->txid && !out->txid) ||
         (log->eff && !out->eff) || (log->tag && !out->tag) || (log->add_tok && !out->add_tok) ||
         (log->rem_off && (!out->rem_off || (!out->rem_tok && log->rem_tok))))

@@ -151,7 +151,11 @@ typedef struct agn_log {
      * id, add_tok = Ts.  agn_materialize does not read rem_off / rem_tok for
      * the type (they may be NULL there); in the engine-owned op log and for
      * agn_prune_ops / agn_log_ingest an entry is a tag-type entry whose removal
-     * range is empty.  The base state and the result use the pair layout with
+     * range is empty, so rem_off is REQUIRED there (all zero).  agn_prune_ops
+     * refuses with AGN_EINVAL, in both output forms and before it touches the
+     * device, a log with entries that lacks its type's arrays: tag, add_tok and
+     * rem_off for set_aw / register_mv / register_lww, eff for counter_pn (and
+     * `out` must carry every array the log has).  The base state and the result use the pair layout with
      * 0 or 1 pair per request (two or more base pairs: AGN_EINVAL where the
      * host sees them, on the device the first is used); out_n == 0 means
      * Type:new().  Fold: the maximum by (ts, tag), unsigned and lexicographic,

@@ -10,7 +10,7 @@
  *   belongs_to_snapshot_op/3   src/materializer.erl:101-106
  *   apply_operations/4         src/clocksi_materializer.erl:113-121
  *   update_snapshot/3          src/materializer.erl:51-58
- *   antidote_crdt_*:update/2   (antidote_crdt 0.1.2, restated in SURVEY.md §8(a) a5.1-a5.3)
+ *   antidote_crdt_*:update/2   (antidote_crdt 0.1.2, restated in SURVEY.md §8(a) a5.1-a5.4)
  *   get_min_time/1             src/stable_time_functions.erl:51-85
  *   update_stable/3            src/meta_data_sender.erl:341-356
  *   get_smaller/2              src/vector_orddict.erl:74-87
@@ -139,6 +139,37 @@ static void register_mv_apply(pairvec *st, uint32_t value, uint64_t add_tok,
     pv_insert_at(st, at, value, add_tok);
 }
 
+/* antidote_crdt_register_lww:update/2: the state is
+ * {Ts, Value}, new() is {0, <<>>} and update(Effect, State) is
+ * {ok, max(Effect, State)} in term order: the larger Ts, at equal Ts the larger
+ * value.  Here Value is its id (tag) and the order is (Ts, tag), unsigned and
+ * lexicographic (include/antidote_gpu.h, AGN_REGISTER_LWW).  Stated deviations
+ * (DESIGN.md §4.2c): the state "no pair" stands for new() and loses to every
+ * effect, Ts = 0 included (downstream/2 never produces it); an effect the
+ * encoder could not represent is AGN_TAG_INVALID and fails update/2.
+ * `tie` follows AGN_F_TS_TIE through the sequential fold: cleared when the
+ * timestamp strictly rises, set when an effect meets the state's timestamp
+ * under another tag. */
+typedef struct {
+    int have;      /* 0: Type:new() */
+    uint64_t ts;
+    uint32_t tag;
+    int tie;
+} lww_t;
+
+static void register_lww_apply(lww_t *st, uint32_t value, uint64_t ts) {
+    if (!st->have) { /* max(Effect, new()) */
+        st->have = 1; st->ts = ts; st->tag = value; st->tie = 0;
+        return;
+    }
+    if (ts > st->ts) { /* Effect > State on the first element */
+        st->ts = ts; st->tag = value; st->tie = 0;
+    } else if (ts == st->ts && value != st->tag) {
+        st->tie = 1;
+        if (value > st->tag) st->tag = value; /* equal Ts: the larger value */
+    }
+}
+
 /* ------------------------------------------------------------------------ */
 
 static void materialize_one(const agn_log *log, const agn_read *req, agn_result *out,
@@ -229,6 +260,31 @@ static void materialize_one(const agn_log *log, const agn_read *req, agn_result 
             ++count;
         }
         if (out->value) out->value[i] = v;
+    } else if (log->crdt_type == AGN_REGISTER_LWW) {
+        /* State = max(Effect, State), effect after effect; rem_off / rem_tok
+         * are not read (the type may leave them NULL). */
+        lww_t st = {0, 0, 0, 0};
+        if (req->base_off && req->base_off[i + 1] > req->base_off[i]) {
+            const uint64_t b = req->base_off[i];
+            st.have = 1; st.ts = req->base_tok[b]; st.tag = req->base_tag[b];
+        }
+        for (uint64_t j = n_incl; j-- > 0;) {
+            const uint64_t e = off + incl_buf[j];
+            if (log->tag[e] == AGN_TAG_INVALID) { err = (uint32_t)e; break; }
+            register_lww_apply(&st, log->tag[e], log->add_tok[e]);
+            ++count;
+        }
+        if (err == UINT32_MAX) {
+            const uint64_t o = out->out_off[i], cap = out->out_off[i + 1] - o;
+            if (st.have && cap == 0) {
+                flags |= AGN_F_ERR_CAPACITY;
+            } else if (st.have) {
+                out->out_tag[o] = st.tag;
+                out->out_tok[o] = st.ts;
+            }
+            if (st.have && st.tie) flags |= AGN_F_TS_TIE;
+            out->out_n[i] = (uint32_t)st.have;
+        }
     } else {
         pairvec st = {0};
         if (req->base_off)
@@ -302,6 +358,12 @@ int oracle_materialize(const agn_log *log, const agn_read *req, agn_result *out,
                        int n_threads) {
     if (!log || !req || !out || log->n_dcs == 0 || log->n_dcs > 256) return AGN_EINVAL;
     if (!req->keys && req->n_req != log->n_keys) return AGN_EINVAL;
+    /* no silent fall-through: a type without a fold here is refused */
+    if (log->crdt_type < AGN_COUNTER_PN || log->crdt_type > AGN_REGISTER_LWW) return AGN_EINVAL;
+    if (req->req_type < AGN_COUNTER_PN || req->req_type > AGN_REGISTER_LWW) return AGN_EINVAL;
+    if (log->crdt_type == AGN_REGISTER_LWW && req->base_off)
+        for (uint64_t i = 0; i < req->n_req; ++i) /* a state is one {Ts, Value} */
+            if (req->base_off[i + 1] - req->base_off[i] > 1) return AGN_EINVAL;
     uint64_t max_n = 0;
     for (uint64_t k = 0; k < log->n_keys; ++k) {
         uint64_t n = KEY_N(log, k);

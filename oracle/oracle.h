@@ -20,7 +20,10 @@
 extern "C" {
 #endif
 
-/* clocksi_materializer:materialize/4 for every request (host pointers). */
+/* clocksi_materializer:materialize/4 for every request (host pointers), for
+ * counter_pn, set_aw, register_mv and register_lww.  Non-zero (nothing
+ * computed) for any other crdt_type / req_type and for a register_lww request
+ * with two or more base pairs. */
 int oracle_materialize(const agn_log *log, const agn_read *req, agn_result *out,
                        int n_threads);
 

@@ -32,6 +32,7 @@ from typing import Any
 COUNTER_PN = "antidote_crdt_counter_pn"
 SET_AW = "antidote_crdt_set_aw"
 REGISTER_MV = "antidote_crdt_register_mv"
+REGISTER_LWW = "antidote_crdt_register_lww"
 IGNORE = "ignore"
 
 FIRST_OP = 4            # include/antidote.hrl:90
@@ -104,6 +105,8 @@ def crdt_new(typ):
         return 0
     if typ in (SET_AW, REGISTER_MV):
         return []
+    if typ == REGISTER_LWW:
+        return (0, b"")  # {0, <<>>}
     raise BadMatch(("undef", typ))  # materializer_error_nocreate_test
 
 
@@ -114,7 +117,20 @@ def crdt_value(typ, state):
         return [e for e, _ in state]
     if typ == REGISTER_MV:
         return [v for v, _ in state]
+    if typ == REGISTER_LWW:
+        return state[1]
     raise BadMatch(("undef", typ))
+
+
+def _lww_term_key(term):
+    """Erlang term order over the value kinds the tests use, restated here:
+    number < binary; integers by value, binaries bytewise (a prefix is the
+    smaller)."""
+    if isinstance(term, int) and not isinstance(term, bool):
+        return (0, term)
+    if isinstance(term, bytes):
+        return (1, term)
+    raise TypeError(("term order not restated for", term))
 
 
 def crdt_update(typ, effect, state):
@@ -139,6 +155,22 @@ def crdt_update(typ, effect, state):
         value, token, ovr = effect
         kept = [(v, t) for v, t in state if t not in ovr]
         return sorted(kept + [(value, token)])
+    if typ == REGISTER_LWW:
+        # update(Effect, State) = {ok, max(Effect, State)} over {Ts, Value}
+        # tuples of one size: by Ts, at equal Ts by the value's term order
+        # (restated, antidote_crdt 0.1.2 is not held).
+        # An effect that is not {integer Ts, V} with Ts < 2^64 is what the
+        # host encoder stores as an invalid entry; it raises here.  Ts = 0 is
+        # the one stated deviation that stays with the encoder (DESIGN.md
+        # §4.2c): update/2 accepts it, the ABI carries it, so it folds.
+        if not (isinstance(effect, tuple) and len(effect) == 2):
+            raise TypeError("badarg")
+        ts, value = effect
+        if not isinstance(ts, int) or isinstance(ts, bool) or not 0 <= ts < 1 << 64:
+            raise TypeError("badarg")
+        new = (ts, _lww_term_key(value))
+        old = (state[0], _lww_term_key(state[1]))
+        return effect if new > old else state
     raise BadMatch(("undef", typ))
 
 

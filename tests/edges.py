@@ -78,10 +78,28 @@ def _entry_ops(pat):
     return opi, cls, up == ord("E")
 
 
+def lww_fields(k, n):
+    """register_lww entries of key k (tag = value id, add_tok = timestamp):
+    even keys walk the edges of both domains (lww_model.TS_EDGE / TAG_EDGE: 0,
+    2^32 +- 1, 2^63, 2^64 - 1 pass through whatever stages the 64-bit field),
+    odd keys a small range in which ties at the top timestamp are common."""
+    from lww_model import TAG_EDGE, TS_EDGE
+    m = np.arange(n)
+    if k % 2 == 0:
+        ts = np.array(TS_EDGE, np.uint64)[(m * 3 + k // 2) % len(TS_EDGE)]
+        tag = np.array(TAG_EDGE, np.uint32)[(m + k // 2) % len(TAG_EDGE)]
+    else:
+        ts = (1 + (m * 5 + k) % 4).astype(np.uint64)
+        tag = ((m * 7 + k) % 3).astype(np.uint32)
+    return tag, ts
+
+
 def default_effects(crdt, k, n):
     """Entry m adds token (k+1, m+1) under elem / value 7m mod 5; every
     fourth entry removes the add five entries back (the same elem) and a
-    token nobody added."""
+    token nobody added.  register_lww: lww_fields, no removals."""
+    if crdt == _abi.REGISTER_LWW:
+        return lww_fields(k, n) + ([[] for _ in range(n)],)
     m = np.arange(n)
     tag = ((m * 7) % 5).astype(np.uint32)
     add = (np.uint64(k + 1) << np.uint64(32)) | (m + 1).astype(np.uint64)
@@ -578,6 +596,12 @@ def gc_case(crdt, D, items, sparse=False, lists=None):
         thr[~tp] = _garbage(int((~tp).sum()), 5)
     if crdt == _abi.COUNTER_PN:
         log.eff = (np.arange(E, dtype=np.int64) * 37) % 2001 - 1000
+    elif crdt == _abi.REGISTER_LWW:   # every removal range empty: rem_off all zero
+        log.tag, log.add_tok = np.zeros(E, np.uint32), np.zeros(E, np.uint64)
+        for k in range(K):
+            a, n = int(key_off[k]), int(lens[k])
+            log.tag[a:a + n], log.add_tok[a:a + n] = lww_fields(k, n)
+        log.rem_off, log.rem_tok = np.zeros(E + 1, np.uint32), np.zeros(1, np.uint64)
     else:
         log.tag = (np.arange(E, dtype=np.uint32) * 7) % 5
         log.add_tok = np.arange(1, E + 1, dtype=np.uint64) | np.uint64(1 << 40)

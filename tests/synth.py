@@ -23,6 +23,30 @@ def _mask_rows(rng, n, D, p_absent):
     return m, present
 
 
+LWW_VALS, LWW_TS_MAX = 3, 8   # the small range of register_lww values / timestamps
+
+
+def _lww_entries(rng, log, invalid):
+    """register_lww entries for a log of clocks: tag = value id, add_tok =
+    timestamp, every removal range empty.  About half the keys draw both from
+    the edges of their domains (lww_model.TS_EDGE / TAG_EDGE: 0, 2^32 +- 1,
+    2^63, 2^64 - 1 travel through whatever stages the 64-bit field), the rest
+    from a small range, so ties at the winning timestamp, base wins and an
+    excluded newest assign are common.  Returns the per-key edge choice."""
+    from lww_model import TAG_EDGE, TS_EDGE
+    K, E = log.n_keys, log.n_entries
+    edge_key = rng.random(K) < 0.5
+    edge = np.repeat(edge_key, np.diff(log.key_off.astype(np.int64)))
+    tag = np.where(edge, rng.choice(np.array(TAG_EDGE, np.uint32), E),
+                   rng.integers(0, LWW_VALS, E).astype(np.uint32)).astype(np.uint32)
+    ts = np.where(edge, rng.choice(np.array(TS_EDGE, np.uint64), E),
+                  rng.integers(1, LWW_TS_MAX + 1, E).astype(np.uint64)).astype(np.uint64)
+    tag[rng.random(E) < invalid] = _abi.TAG_INVALID
+    log.tag, log.add_tok = tag, ts
+    log.rem_off, log.rem_tok = np.zeros(E + 1, np.uint32), np.zeros(1, np.uint64)
+    return edge_key
+
+
 def random_case(seed, crdt, K, D, nmax, *, sparse=False, warm=0.0, txid=0.0, invalid=0.0,
                 corrupt=0.0, multi=0.0, base=0.0, n_elems=6, empty=0.1, identity=True):
     rng = np.random.default_rng(seed)
@@ -94,6 +118,8 @@ def random_case(seed, crdt, K, D, nmax, *, sparse=False, warm=0.0, txid=0.0, inv
         eff = rng.integers(-1000, 1001, E).astype(np.int64)
         eff[rng.random(E) < invalid] = _abi.EFFECT_INVALID
         log.eff = eff
+    elif crdt == _abi.REGISTER_LWW:
+        edge_key = _lww_entries(rng, log, invalid)
     else:
         tag = rng.integers(0, n_elems, E).astype(np.uint32)
         add = np.zeros(E, np.uint64)
@@ -146,7 +172,18 @@ def random_case(seed, crdt, K, D, nmax, *, sparse=False, warm=0.0, txid=0.0, inv
         Sm = np.zeros((K, W), np.uint64)
     boff = np.zeros(K + 1, np.uint64)
     btag, btok = [], []
-    if crdt != _abi.COUNTER_PN:
+    if crdt == _abi.REGISTER_LWW:
+        from lww_model import TAG_EDGE, TS_EDGE
+        for k in range(K):   # at most one pair: a state is one {Ts, Value}
+            if rng.random() < base:
+                if edge_key[k]:
+                    btag.append(int(rng.choice(TAG_EDGE)))
+                    btok.append(int(rng.choice(np.array(TS_EDGE, np.uint64))))
+                else:
+                    btag.append(int(rng.integers(0, LWW_VALS)))
+                    btok.append(int(rng.integers(1, LWW_TS_MAX + 3)))
+            boff[k + 1] = len(btag)
+    elif crdt != _abi.COUNTER_PN:
         for k in range(K):
             if rng.random() < base:
                 pairs = [(int(rng.integers(0, n_elems)), (1 << 60) | (k << 8) | (x + 1))

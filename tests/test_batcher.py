@@ -86,7 +86,8 @@ def run_threads(n_threads, fn, items):
 
 
 CASES = [(_abi.COUNTER_PN, 8, False), (_abi.COUNTER_PN, 5, True), (_abi.SET_AW, 16, False),
-         (_abi.SET_AW, 6, True), (_abi.REGISTER_MV, 8, True)]
+         (_abi.SET_AW, 6, True), (_abi.REGISTER_MV, 8, True), (_abi.REGISTER_LWW, 8, False),
+         (_abi.REGISTER_LWW, 6, True)]
 
 
 @pytest.mark.parametrize("crdt,D,sparse", CASES)

@@ -51,14 +51,22 @@ def test_materialize_host_many_threads(eng, oracle_lib):
     assert not errs, errs[0]
 
 
-@pytest.mark.parametrize("crdt", [_abi.SET_AW, _abi.REGISTER_MV])
+@pytest.mark.parametrize("crdt", [_abi.SET_AW, _abi.REGISTER_MV, _abi.REGISTER_LWW])
 def test_batcher_sizes_outputs_under_concurrent_appends(eng, crdt):
     """A writer appends adds / assigns to the very keys 8 reader threads read.
     The batcher sizes each read's output capacity from the key's length; the
     length must be the one the kernel sees (taken under the flush's lock), so
     no read may come back with AGN_F_ERR_CAPACITY, and a read's live pairs
-    never exceed the entries appended before it returned."""
+    never exceed the entries appended before it returned.
+
+    register_lww: a state is one pair, so the capacity is 0 for a key without
+    an entry and 1 once it has one.  Timestamps rise with every append (across
+    2^32), so the state a read returns names the newest entry it counted.  A
+    read racing a key's first append comes back with that state or with
+    AGN_ECAPACITY and out_n = 1 -- never with ops counted and no pair."""
     D, K, N = 4, 6, 600
+    lww = crdt == _abi.REGISTER_LWW
+    ts0 = (1 << 32) - N // 2
     big = np.full(D, 10 ** 12, np.uint64)
     appended = [0] * K
     lock = threading.Lock()
@@ -76,8 +84,10 @@ def test_batcher_sizes_outputs_under_concurrent_appends(eng, crdt):
                             appended[k] += 1
                         # set_aw: a fresh token for a new element (never removed);
                         # register_mv: a concurrent assign (overrides nothing)
-                        ol.append(np.array([k], np.uint64), oc, tag=np.array([j], np.uint32),
-                                  add_tok=np.array([j + 1], np.uint64),
+                        # register_lww: value j mod 5 at timestamp ts0 + j
+                        ol.append(np.array([k], np.uint64), oc,
+                                  tag=np.array([j % 5 if lww else j], np.uint32),
+                                  add_tok=np.array([ts0 + j if lww else j + 1], np.uint64),
                                   rem_off=np.array([0, 0], np.uint32), rem_tok=None)
                 except Exception as e:  # noqa: BLE001
                     errs.append(e)
@@ -88,6 +98,21 @@ def test_batcher_sizes_outputs_under_concurrent_appends(eng, crdt):
                 try:
                     while not stop.is_set():
                         k = t % K
+                        if lww:
+                            r = bt.read(k, R=big, out_cap=1, capacity_ok=True)
+                            with lock:
+                                n_app = appended[k]
+                            if r.get("ecapacity"):
+                                assert r["out_n"] == 1, r
+                                continue
+                            assert not (r["flags"] & _abi.F_ERR_CAPACITY), r["flags"]
+                            assert r["count"] <= n_app and r["out_n"] == (r["count"] > 0), r
+                            assert bool(r["flags"] & _abi.F_NEWSS) == (r["count"] > 0), r
+                            if r["count"]:
+                                j = k + (r["count"] - 1) * K   # the newest entry counted
+                                assert (int(r["out_tag"][0]), int(r["out_tok"][0])) == \
+                                    (j % 5, ts0 + j), (r, j)
+                            continue
                         r = bt.read(k, R=big, out_cap=N)
                         with lock:
                             n_app = appended[k]
@@ -102,6 +127,14 @@ def test_batcher_sizes_outputs_under_concurrent_appends(eng, crdt):
             for t in ts:
                 t.join()
             assert not errs, errs[0]
+            if lww:
+                for k in range(K):
+                    r = bt.read(k, R=big, out_cap=1)
+                    j = k + (appended[k] - 1) * K
+                    assert (r["count"], r["out_n"]) == (appended[k], 1)
+                    assert (int(r["out_tag"][0]), int(r["out_tok"][0])) == (j % 5, ts0 + j)
+                    assert not r["flags"] & _abi.F_TS_TIE
+                return
             final = [bt.read(k, R=big, out_cap=N)["out_n"] for k in range(K)]
             assert final == appended
 

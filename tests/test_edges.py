@@ -332,6 +332,7 @@ GC_LOGS = {
     "set5": lambda: edges.family_e(_abi.SET_AW, 5),
     "set16s": lambda: edges.family_e(_abi.SET_AW, 16, True),
     "register8s": lambda: edges.family_e(_abi.REGISTER_MV, 8, True),
+    "lww8": lambda: edges.family_e(_abi.REGISTER_LWW, 8),
     "ring_set5": lambda: edges.family_e_ring(_abi.SET_AW, 5),
     "ring_register16": lambda: edges.family_e_ring(_abi.REGISTER_MV, 16),
 }

@@ -308,7 +308,8 @@ def check_prune(oracle_lib, crdt, log, prune, thr, tm, names):
 
 
 @pytest.mark.parametrize("crdt,D,sparse", [(_abi.COUNTER_PN, 8, False), (_abi.COUNTER_PN, 3, True),
-                                           (_abi.SET_AW, 5, False), (_abi.REGISTER_MV, 8, True)])
+                                           (_abi.SET_AW, 5, False), (_abi.REGISTER_MV, 8, True),
+                                           (_abi.REGISTER_LWW, 8, False)])
 def test_family_e(oracle_lib, crdt, D, sparse):
     log, prune, thr, tm, names = edges.family_e(crdt, D, sparse)
     arrs, flags, kept_n = check_prune(oracle_lib, crdt, log, prune, thr, tm, names)

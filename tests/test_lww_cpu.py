@@ -304,3 +304,57 @@ def test_host_generator(lib):
     # the first op of every key draws the same clocks under either type
     first = np.arange(K) * N
     assert np.array_equal(out[LWW]["oc"][first], out[_abi.COUNTER_PN]["oc"][first])
+
+
+@pytest.mark.parametrize("segmented", [False, True], ids=["csr", "segmented"])
+@pytest.mark.parametrize("crdt", [_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV, LWW])
+def test_prune_ops_needs_the_types_arrays(lib, crdt, segmented):
+    """agn_prune_ops checks, before the device is touched (so the NULL context
+    is a complete log's only error), that a log with entries carries its
+    type's arrays and `out` the same; the CSR form and the one-pass segmented
+    form (out.key_len) accept exactly the same inputs.  A register_lww log
+    without rem_off, fine for agn_materialize, is refused here: the segmented
+    kernel would take it for a counter log and read eff."""
+    from test_prune import host_out_like, out_struct
+    log, _req, _ = random_case(17 + crdt, crdt, 6, 3, 9, empty=0.2)
+    assert log.n_entries > 0
+    thr = np.zeros((log.n_keys, 3), np.uint64)
+    arrs = host_out_like(log)
+    klen = np.zeros(log.n_keys, np.uint64)
+    needs = ("eff",) if crdt == _abi.COUNTER_PN else ("tag", "add_tok", "rem_off")
+
+    def call(drop_log=(), drop_out=()):
+        ls, os_ = log_struct(log), out_struct(log, arrs)
+        if segmented:
+            os_.key_len = klen.ctypes.data
+        for name in drop_log:
+            setattr(ls, name, None)
+        for name in drop_out:
+            setattr(os_, name, None)
+        rc = lib.agn_prune_ops(None, C.byref(ls), None, thr.ctypes.data, None, C.byref(os_), None,
+                               None, None)
+        return rc, lib.agn_last_error()
+
+    assert call() == (_abi.EINVAL, b"null context")
+    for name in needs:
+        rc, msg = call(drop_log=(name,), drop_out=(name,))
+        assert rc == _abi.EINVAL and b"needs" in msg and name.encode() in msg, (name, msg)
+        rc, msg = call(drop_log=(name,))
+        assert rc == _abi.EINVAL and b"needs" in msg, (name, msg)
+        rc, msg = call(drop_out=(name,))
+        assert rc == _abi.EINVAL and msg == b"prune_ops: out lacks an array the log has", (name, msg)
+    if crdt == LWW:   # what agn_materialize accepts for the type
+        rc, msg = call(drop_log=("rem_off", "rem_tok"), drop_out=("rem_off", "rem_tok"))
+        assert rc == _abi.EINVAL and b"rem_off" in msg
+    # an empty log has no arrays to miss
+    ls, os_ = log_struct(log), out_struct(log, arrs)
+    ls.n_entries = 0
+    for name in needs:
+        setattr(ls, name, None)
+    assert lib.agn_prune_ops(None, C.byref(ls), None, thr.ctypes.data, None, C.byref(os_), None,
+                             None, None) == _abi.EINVAL and lib.agn_last_error() == b"null context"
+    ls = log_struct(log)
+    ls.crdt_type = 5
+    assert lib.agn_prune_ops(None, C.byref(ls), None, thr.ctypes.data, None, C.byref(os_), None,
+                             None, None) == _abi.EINVAL
+    assert lib.agn_last_error() == b"prune_ops: unknown crdt_type 5"

@@ -182,7 +182,8 @@ def csr_key(arrs, k, tags):
 
 CASES = [(_abi.COUNTER_PN, 8, False, 4), (_abi.COUNTER_PN, 3, True, 0),
          (_abi.COUNTER_PN, 70, True, 2), (_abi.SET_AW, 5, False, 4), (_abi.SET_AW, 16, True, 1),
-         (_abi.REGISTER_MV, 8, False, 3), (_abi.REGISTER_MV, 64, True, 0)]
+         (_abi.REGISTER_MV, 8, False, 3), (_abi.REGISTER_MV, 64, True, 0),
+         (_abi.REGISTER_LWW, 8, False, 3), (_abi.REGISTER_LWW, 13, True, 2)]
 
 
 @pytest.mark.parametrize("crdt,D,sparse,init", CASES)

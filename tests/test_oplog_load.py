@@ -22,7 +22,7 @@ from test_prune import oracle_prune, thresholds
 
 pytestmark = pytest.mark.gpu
 
-TYPES = [_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV]
+TYPES = [_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV, _abi.REGISTER_LWW]
 INIT = 4
 
 
@@ -179,7 +179,8 @@ def test_load_csr_equals_twin(eng, crdt, D, sparse):
 
 @pytest.mark.parametrize("lengths", [(0, 0, 0, 0, 0), (65,), (0,), (129, 0)],
                          ids=["all-empty", "one-key", "one-empty-key", "long-then-empty"])
-@pytest.mark.parametrize("crdt,D,sparse", [(_abi.COUNTER_PN, 3, True), (_abi.SET_AW, 8, False)])
+@pytest.mark.parametrize("crdt,D,sparse", [(_abi.COUNTER_PN, 3, True), (_abi.SET_AW, 8, False),
+                                           (_abi.REGISTER_LWW, 5, True)])
 def test_load_small_logs(eng, crdt, D, sparse, lengths):
     log, _ = case(crdt, D, sparse, lengths)
     src = upload_src(eng, log)
@@ -190,7 +191,7 @@ def test_load_small_logs(eng, crdt, D, sparse, lengths):
 
 
 VIEW_CASES = [(_abi.COUNTER_PN, 3, True), (_abi.COUNTER_PN, 8, False), (_abi.SET_AW, 16, True),
-              (_abi.REGISTER_MV, 65, False)]
+              (_abi.REGISTER_MV, 65, False), (_abi.REGISTER_LWW, 8, False)]
 
 
 @pytest.mark.parametrize("crdt,D,sparse", VIEW_CASES)
@@ -214,7 +215,8 @@ def test_load_view_after_prune_equals_twin(eng, oracle_lib, crdt, D, sparse):
 
 
 @pytest.mark.parametrize("crdt,D,sparse", [(_abi.COUNTER_PN, 8, False), (_abi.COUNTER_PN, 3, True),
-                                           (_abi.SET_AW, 5, True), (_abi.REGISTER_MV, 16, False)])
+                                           (_abi.SET_AW, 5, True), (_abi.REGISTER_MV, 16, False),
+                                           (_abi.REGISTER_LWW, 16, True)])
 def test_loaded_log_behaves_like_twin(eng, oracle_lib, crdt, D, sparse):
     """The same appends, flush, materialize, prune and cached-batcher reads
     (GC reads included) on the loaded log and on the twin."""

@@ -2,7 +2,10 @@
 inputs: oracle/oracle.c (SoA, the GPU parity checker) and oracle/py_oracle.py
 (dict clocks, literal transcription of the Erlang).  Covers sparse clocks,
 warm reads, TxId matches, invalid effects, corrupted keys, multi-entry ops and
-base states for all three CRDT types."""
+base states for the CRDT types (register_lww: single-entry ops, 0 or 1 base
+pair; its value ids travel as 4-byte big-endian binaries, so the py oracle's
+term order over them is the unsigned order of the ids and every one of them
+is above new()'s <<>>)."""
 import ctypes as C
 
 import numpy as np
@@ -14,7 +17,11 @@ from oracle import py_oracle as po
 from synth import random_case
 
 TYPES = {_abi.COUNTER_PN: po.COUNTER_PN, _abi.SET_AW: po.SET_AW,
-         _abi.REGISTER_MV: po.REGISTER_MV}
+         _abi.REGISTER_MV: po.REGISTER_MV, _abi.REGISTER_LWW: po.REGISTER_LWW}
+
+
+def lww_value(tag):
+    return int(tag).to_bytes(4, "big")
 
 
 def present(mask_row, d):
@@ -45,6 +52,8 @@ def key_ops(log, k, typ):
             eff = ("invalid",) if v == _abi.EFFECT_INVALID else v
         elif any(int(log.tag[e]) == _abi.TAG_INVALID for e in g):
             eff = ("invalid",)
+        elif log.crdt_type == _abi.REGISTER_LWW:
+            eff = (int(log.add_tok[e0]), lww_value(log.tag[e0]))
         else:
             ro = log.rem_off
             parts = []
@@ -86,6 +95,8 @@ def py_run(log, req, i):
             for t, x in pairs:
                 st.setdefault(t, []).append(x)
             base = sorted(st.items())
+        elif log.crdt_type == _abi.REGISTER_LWW:
+            base = (pairs[0][1], lww_value(pairs[0][0])) if pairs else po.crdt_new(typ)
         else:
             base = pairs
     resp = po.SnapshotGetResponse(ops, len(ops), po.MaterializedSnapshot(0, base), sct, True)
@@ -117,13 +128,15 @@ def c_decode(log, req, res, i, sparse):
             for t, x in pairs:
                 st.setdefault(t, []).append(x)
             val = sorted(st.items())
+        elif log.crdt_type == _abi.REGISTER_LWW:
+            val = (pairs[0][1], lww_value(pairs[0][0])) if pairs else (0, b"")
         else:
             val = pairs
     return ("ok", val, int(res.hole[i]), ct, bool(f & _abi.F_NEWSS), int(res.count[i]))
 
 
 CASES = []
-for crdt in (_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV):
+for crdt in (_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV, _abi.REGISTER_LWW):
     for D in (1, 3, 8, 17):
         for sparse in (False, True):
             CASES.append((crdt, D, sparse))

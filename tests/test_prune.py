@@ -39,7 +39,11 @@ def thresholds(seed, log, sparse):
     tm = None
     if sparse:
         tm = np.zeros((K, W), np.uint64)
-        pres = rng.random((K, D)) >= 0.1
+        # a DC the threshold lacks reads 0 and keeps every op that carries it:
+        # the register_lww rows let the rate shrink with D, so that a wide
+        # masked log is still pruned (the other rows keep their draws)
+        p_absent = min(0.1, 1.0 / D) if log.crdt_type == _abi.REGISTER_LWW else 0.1
+        pres = rng.random((K, D)) >= p_absent
         for d in range(D):
             tm[:, d >> 6] |= pres[:, d].astype(np.uint64) << np.uint64(d & 63)
     prune = (rng.random(K) < 0.8).astype(np.uint8)
@@ -79,7 +83,12 @@ def oracle_prune(lib, log, prune, thr, tm):
 
 CASES = [(_abi.COUNTER_PN, 3, False), (_abi.COUNTER_PN, 8, True), (_abi.COUNTER_PN, 16, False),
          (_abi.SET_AW, 5, False), (_abi.SET_AW, 16, True), (_abi.REGISTER_MV, 64, False),
-         (_abi.REGISTER_MV, 2, True)]
+         (_abi.REGISTER_MV, 2, True),
+         # register_lww: every removal range empty.  D = 8 dense is the one
+         # shape that reaches the CT-rows form with tags; D = 129 masked has
+         # three mask words per row
+         (_abi.REGISTER_LWW, 8, False), (_abi.REGISTER_LWW, 5, True),
+         (_abi.REGISTER_LWW, 129, True)]
 
 
 @pytest.mark.parametrize("crdt,D,sparse", CASES)

@@ -36,7 +36,13 @@ from oracle import py_oracle as po
 pytestmark = pytest.mark.gpu
 
 D = 3
-PTYPE = {_abi.SET_AW: po.SET_AW, _abi.REGISTER_MV: po.REGISTER_MV, _abi.COUNTER_PN: po.COUNTER_PN}
+LWW = _abi.REGISTER_LWW
+PTYPE = {_abi.SET_AW: po.SET_AW, _abi.REGISTER_MV: po.REGISTER_MV, _abi.COUNTER_PN: po.COUNTER_PN,
+         LWW: po.REGISTER_LWW}
+PAIR_TYPES = [_abi.SET_AW, _abi.REGISTER_MV, LWW]
+# register_lww timestamps an encoder accepts (Ts >= 1), at the edges of the domain
+LWW_TS_EDGE = [1, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, 1 << 63, (1 << 63) + 1, (1 << 64) - 1]
+LWW_NEW = (0, b"")
 
 
 def vc(row, mask=None):
@@ -47,7 +53,11 @@ class TagWorkload:
     """Causal clocks as in test_vnode_replay; effects built the way the CRDTs'
     downstream does: set_aw add = {Elem, [new token], observed tokens of Elem},
     remove = {Elem, [], observed}; register_mv assign = {V, new token, all
-    observed}, reset = {reset, all observed} (observed = the writer's view)."""
+    observed}, reset = {reset, all observed} (observed = the writer's view);
+    register_lww assign = {Ts, V}: V an integer 0..4 (its own tag id, so the
+    device's tie break by tag is update/2's by term), Ts from the edges of the
+    u64 domain on even keys and from 1..8 on odd keys, where ties are common.
+    A state is then no pair (new()) or one."""
 
     def __init__(self, seed, K, typ, d=D):
         self.rng = np.random.default_rng(seed)
@@ -64,6 +74,11 @@ class TagWorkload:
         oc = ss.copy()
         oc[c] = self.clk[c]
         live = self.live[key]
+        if self.typ == LWW:
+            v = int(self.rng.integers(0, 5))
+            ts = int(self.rng.integers(1, 9)) if key % 2 else \
+                LWW_TS_EDGE[int(self.rng.integers(0, len(LWW_TS_EDGE)))]
+            return c, ss, int(self.clk[c]), oc, (ts, v), (v, ts, [])
         if self.typ == _abi.SET_AW:
             e = int(self.rng.integers(0, 6))
             obs = list(live.get(e, []))
@@ -94,7 +109,11 @@ class TagWorkload:
 
 def state_of(typ, tags, toks):
     """Engine pairs -> the reference's state: set_aw orddict [{Elem, [Tok]}]
-    (pairs grouped by elem, tokens in fold order), register_mv [{V, Tok}]."""
+    (pairs grouped by elem, tokens in fold order), register_mv [{V, Tok}],
+    register_lww {Ts, V} (no pair: new())."""
+    if typ == LWW:
+        assert len(tags) <= 1
+        return (int(toks[0]), int(tags[0])) if len(tags) else LWW_NEW
     if typ == _abi.REGISTER_MV:
         return [(int(v), int(t)) for v, t in zip(tags, toks)]
     out = []
@@ -145,9 +164,10 @@ class NifPartition:
 
     def from_log(self, key, R_dict, gc):
         counter = self.typ == _abi.COUNTER_PN
-        resp = log_response(self.disk, key, R_dict, 0 if counter else None)
+        new = 0 if counter else LWW_NEW if self.typ == LWW else None
+        resp = log_response(self.disk, key, R_dict, new)
         if resp.number_of_ops == 0:
-            return ("ok", 0 if counter else [])  # materialize_snapshot :468-471
+            return ("ok", [] if new is None else new)  # materialize_snapshot :468-471
         r = cm.materialize(PTYPE[self.typ], IGNORE, R_dict, resp)
         if r[0] != "ok":
             return r
@@ -164,6 +184,8 @@ class NifPartition:
             else:
                 if self.typ == _abi.SET_AW:
                     pairs = [(e, t) for e, toks in value for t in toks]
+                elif self.typ == LWW:
+                    pairs = [] if value == LWW_NEW else [(value[1], value[0])]
                 else:
                     pairs = list(value)
                 self.bt.store(key, row, clock_mask=np.uint64(m), last_op=hole, count=count,
@@ -248,7 +270,7 @@ def reference_quirks(typ, d, logk, K=16, steps=2500):
 
 
 @pytest.mark.parametrize("d,logk,read6", BATCHER_CASES)
-@pytest.mark.parametrize("typ", [_abi.SET_AW, _abi.REGISTER_MV])
+@pytest.mark.parametrize("typ", PAIR_TYPES)
 def test_batcher_states_vs_reference(eng, typ, d, logk, read6, monkeypatch):
     """update/2 (+ its GC read) and read/6 through a cached set/register
     partition: every served state equals the reference's, and the ETS list
@@ -321,7 +343,7 @@ def rand_mask(rng, d):
 
 
 @pytest.mark.parametrize("d", [3, 4, 8, 16, 64])
-@pytest.mark.parametrize("typ", [_abi.SET_AW, _abi.REGISTER_MV])
+@pytest.mark.parametrize("typ", PAIR_TYPES)
 def test_batcher_fused_vs_sequence_mixed_dcs(eng, typ, d, monkeypatch):
     """Entries with random DC sets (each holding its own DC; R with some DCs
     missing now and then): two partitions fed the same updates, one served by
@@ -406,7 +428,7 @@ def test_batcher_state_bound_grows(eng, d, read6, monkeypatch):
             [(e, [e + 1]) for e in range(n)]
 
 
-@pytest.mark.parametrize("typ", [_abi.SET_AW, _abi.REGISTER_MV])
+@pytest.mark.parametrize("typ", PAIR_TYPES)
 def test_read_cached_states_vs_reference(eng, typ):
     """agn_read_cached over device arrays: rounds of reads of every key at a
     growing clock (with GC reads), the selected keys pruned in the log, and the
@@ -550,7 +572,7 @@ def test_nif_gc_read_capacity_retry_runs_the_gc_once(eng, read6, monkeypatch):
         assert not g.get("ecapacity") and g["out_n"] == 63
 
 
-@pytest.mark.parametrize("typ", [_abi.SET_AW, _abi.REGISTER_MV])
+@pytest.mark.parametrize("typ", PAIR_TYPES)
 def test_state_arena_repacks_vs_reference(eng, typ, monkeypatch):
     """A cached partition whose state arena starts tiny (AGN_SS_ARENA_INIT):
     the batcher re-packs / grows it again and again between batches

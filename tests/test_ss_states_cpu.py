@@ -5,13 +5,12 @@ parametrization -- and there are none, so the GPU test compares every key
 and asserts its exclusion set is empty."""
 import pytest
 
-from antidote_amd import _abi
 import test_ss_states as t
 
 CASES = sorted({(d, lg) for d, lg, _ in t.BATCHER_CASES})
 
 
-@pytest.mark.parametrize("typ", [_abi.SET_AW, _abi.REGISTER_MV])
+@pytest.mark.parametrize("typ", t.PAIR_TYPES)
 def test_reference_excludes_no_key(typ):
     for d, lg in CASES:
         assert t.reference_quirks(typ, d, lg) == set(), (typ, d, lg)
