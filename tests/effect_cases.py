@@ -13,6 +13,7 @@ import numpy as np
 
 import edges
 from antidote_amd import _abi
+from synth import cold  # noqa: F401  (the same requests without SCT; callers use effect_cases.cold)
 
 D = 8
 LENGTHS = (1, 63, 64, 65, 128, 129, 257)
@@ -96,11 +97,6 @@ def poison(log, pats, kind, which="XP"):
         pos = np.concatenate([np.arange(len(p), dtype=np.int64) for p in pats])
         eff[hit] = (1 << 62) + pos[hit]
     return dataclasses.replace(log, eff=eff)
-
-
-def cold(req):
-    """The same requests without SCT (the cold kernels)."""
-    return dataclasses.replace(req, sct=None, sct_mask=None, sct_ignore=None)
 
 
 def build(case, style=None):

@@ -5,8 +5,14 @@ reference's semantics has: ragged and empty keys, sparse clocks (DCs missing
 from op clocks, from the read snapshot and from SCT), warm reads (SCT set),
 reading-transaction matches (TxId == op.txid), invalid effects, keys whose
 ops have another type, multi-entry ops and base states.
+
+random_case's batches are warm-capable (the SCT arrays are always there) and
+read every key once; cold() drops the SCT arrays and rekey() turns the key map
+into a subset or into repeated keys with a row of their own per request.
 """
 from __future__ import annotations
+
+import dataclasses
 
 import numpy as np
 
@@ -48,11 +54,16 @@ def _lww_entries(rng, log, invalid):
 
 
 def random_case(seed, crdt, K, D, nmax, *, sparse=False, warm=0.0, txid=0.0, invalid=0.0,
-                corrupt=0.0, multi=0.0, base=0.0, n_elems=6, empty=0.1, identity=True):
+                corrupt=0.0, multi=0.0, base=0.0, n_elems=6, empty=0.1, identity=True,
+                lens=None):
+    """lens: the keys' lengths, given (then nmax and empty choose nothing; the
+    generator's draws stay where they were)."""
     rng = np.random.default_rng(seed)
     W = n_words(D)
-    lens = rng.integers(0, nmax + 1, K)
-    lens[rng.random(K) < empty] = 0
+    drawn = rng.integers(0, nmax + 1, K)
+    drawn[rng.random(K) < empty] = 0
+    lens = drawn if lens is None else np.asarray(lens, np.int64).copy()
+    assert len(lens) == K and (lens >= 0).all()
     key_off = np.zeros(K + 1, np.uint64)
     key_off[1:] = np.cumsum(lens)
     E = int(key_off[-1])
@@ -207,6 +218,83 @@ def random_case(seed, crdt, K, D, nmax, *, sparse=False, warm=0.0, txid=0.0, inv
                       base_tag=np.array(btag, np.uint32), base_tok=np.array(btok, np.uint64))
     cap = state_capacity(log, req) if crdt != _abi.COUNTER_PN else None
     return log, req, cap
+
+
+def cold(req):
+    """The same requests without SCT (sct == NULL: the cold kernels)."""
+    return dataclasses.replace(req, sct=None, sct_mask=None, sct_ignore=None)
+
+
+REPEAT_RUN = 9   # rekey "repeat": one key fills this many consecutive requests
+
+
+def rekey(log, req, mode, seed, hot=0):
+    """(req2, cap2): the requests of `req` (one per key, any order) under a key
+    map that is no permutation.
+
+    "subset": about K/3 distinct keys in random order, each with its row of
+    `req` as it is.
+    "repeat": n_req = 2K + 1, keys drawn with replacement from all but
+    ceil(K/4) keys, which are never requested (hot > 0: half of the draws go to
+    the first `hot` keys of the pool); one key fills the REPEAT_RUN requests
+    from a multiple of 8 on, a whole aligned group of 8 and both halves of a
+    pair.  Every request has a row of its own: the key's R plus a jitter in
+    [-3, 4) per column, floored at 1, a txid and a base_value of its own, with
+    SCT arrays an SCT (the key's plus the same kind of jitter, floored at 0)
+    and an sct_ignore of its own, and for the state types a base of its own: a
+    subsequence of the key's base pairs (which keeps their order)."""
+    rng = np.random.default_rng(seed)
+    K, D = log.n_keys, log.n_dcs
+    assert req.n_req == K and len(set(req.keys.tolist())) == K
+    row_of = np.zeros(K, np.int64)
+    row_of[req.keys.astype(np.int64)] = np.arange(K)
+    if mode == "subset":
+        keys = rng.permutation(K)[:max(1, K // 3)]
+    elif mode == "repeat":
+        pool = rng.permutation(K)[:K - (K + 3) // 4]
+        n = 2 * K + 1
+        keys = pool[rng.integers(0, len(pool), n)]
+        if hot:
+            h = rng.random(n) < 0.5
+            keys[h] = pool[rng.integers(0, hot, int(h.sum()))]
+        at = 8 * int(rng.integers(0, (n - REPEAT_RUN) // 8 + 1))
+        keys[at:at + REPEAT_RUN] = pool[0]
+    else:
+        raise KeyError(mode)
+    n = len(keys)
+    src = row_of[keys]
+    rep = mode == "repeat"
+    R = req.R[src]
+    txid, bv = req.txid[src], req.base_value[src]
+    if rep:
+        assert int(R.max()) < 1 << 62
+        R = np.maximum(R.astype(np.int64) + rng.integers(-3, 4, (n, D)), 1).astype(np.uint64)
+        txid = np.where(rng.random(n) < 0.3, rng.integers(1, 6, n), 0).astype(np.uint64)
+        bv = rng.integers(-50, 50, n).astype(np.int64)
+    sct = sm = si = None
+    if req.sct is not None:
+        sct, sm, si = req.sct[src], req.sct_mask[src], req.sct_ignore[src]
+        if rep:
+            sct = np.maximum(sct.astype(np.int64) + rng.integers(-3, 4, (n, D)), 0).astype(np.uint64)
+            si = np.where(rng.random(n) < 0.25, 1 - si, si).astype(np.uint8)
+    boff = np.zeros(n + 1, np.uint64)
+    btag, btok = [], []
+    for i, j in enumerate(src):
+        a, b = int(req.base_off[j]), int(req.base_off[j + 1])
+        keep = rng.random(b - a) < 0.7 if rep else np.ones(b - a, bool)
+        btag += req.base_tag[a:b][keep].tolist()
+        btok += req.base_tok[a:b][keep].tolist()
+        boff[i + 1] = len(btag)
+    req2 = EncodedRead(n_dcs=D, req_type=req.req_type, keys=keys.astype(np.uint64),
+                       R=np.ascontiguousarray(R), R_mask=np.ascontiguousarray(req.R_mask[src]),
+                       sct=None if sct is None else np.ascontiguousarray(sct),
+                       sct_mask=None if sm is None else np.ascontiguousarray(sm),
+                       sct_ignore=None if si is None else np.ascontiguousarray(si),
+                       txid=np.ascontiguousarray(txid), base_value=np.ascontiguousarray(bv),
+                       base_off=boff, base_tag=np.array(btag, np.uint32),
+                       base_tok=np.array(btok, np.uint64))
+    cap2 = state_capacity(log, req2) if log.crdt_type != _abi.COUNTER_PN else None
+    return req2, cap2
 
 
 def compare(crdt, D, a, b, sparse, n):

@@ -14,7 +14,7 @@ import pytest
 from antidote_amd import _abi
 from antidote_amd.encode import alloc_result, log_struct, read_struct, result_struct, state_capacity
 from antidote_amd.engine import Batcher, OpLog
-from synth import compare, random_case
+from synth import compare, random_case, rekey
 from test_oplog import append_ops, interleave, ops_of, renumbered
 
 pytestmark = pytest.mark.gpu
@@ -112,6 +112,43 @@ def test_batcher_concurrent_reads_vs_oracle(eng, oracle_lib, crdt, D, sparse):
         got_r = gather(results, req.n_req, D, cap)
         # the batcher names the failing op by its id (agn_key_result.err_pos,
         # ABI v5), the oracle by its entry in the log
+        bad = want.err_pos != np.uint32(0xFFFFFFFF)
+        want.err_pos[bad] = np.asarray(log2.op_id)[want.err_pos[bad]]
+        assert not compare(crdt, D, got_r, want, sparse, req.n_req)
+
+
+def repeated_case(crdt, D, sparse):
+    """(log, req2): 100 keys, 201 requests over repeated keys (synth.rekey),
+    half of them on three hot keys, each with its own R, SCT, txid and base."""
+    log, req, _ = random_case(23 * D + crdt, crdt, 100, D, 40, sparse=sparse, warm=0.4, txid=0.2,
+                              base=0.3, multi=0.2 if crdt == _abi.SET_AW else 0.0)
+    req2, _ = rekey(log, req, "repeat", 7 * D + crdt, hot=3)
+    return log, req2
+
+
+@pytest.mark.parametrize("crdt,D,sparse", CASES)
+def test_batcher_repeated_keys_vs_oracle(eng, oracle_lib, crdt, D, sparse):
+    """The uncached batcher puts repeated keys into one batch: twenty read
+    servers on three hot keys (and a tail of others) at different snapshots.
+    Every request's result is the oracle's for its own R."""
+    rng = np.random.default_rng(5 * D + crdt)
+    log, req = repeated_case(crdt, D, sparse)
+    counts = np.bincount(req.keys.astype(np.int64), minlength=log.n_keys)
+    assert req.n_req == 201 and (np.sort(counts)[-3:] >= 20).all() and (counts == 0).sum() >= 25
+    with OpLog(eng, crdt, D, log.n_keys, sparse=sparse, init_slots=8) as ol:
+        got = append_ops(ol, log, interleave(rng, ops_of(log)), rng, flush_p=0.3)
+        log2 = renumbered(log, got)
+        want, cap = oracle(oracle_lib, log2, req, sparse)
+        results = [None] * req.n_req
+        with Batcher(ol, max_batch=64, max_wait_us=300) as bt:
+            def one(i):
+                oc = int(cap[i + 1] - cap[i]) if cap is not None else 0
+                results[i] = bt.read(int(req.keys[i]), out_cap=oc, **key_read_args(req, i, sparse))
+            run_threads(20, one, list(range(req.n_req)))
+            st = bt.stats()
+        assert st["reads"] == req.n_req
+        assert st["batches"] < req.n_req
+        got_r = gather(results, req.n_req, D, cap)
         bad = want.err_pos != np.uint32(0xFFFFFFFF)
         want.err_pos[bad] = np.asarray(log2.op_id)[want.err_pos[bad]]
         assert not compare(crdt, D, got_r, want, sparse, req.n_req)

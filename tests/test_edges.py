@@ -10,7 +10,6 @@ through agn_prune_ops in both forms and agn_oplog_prune with its knobs; F
 (hand-on lists) through the masked list passes."""
 import contextlib
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ from antidote_amd import _abi
 from antidote_amd.encode import (EncodedRead, alloc_result, log_struct, n_words, read_struct,
                                  result_struct)
 from antidote_amd.engine import OpLog
+import synth
 from synth import compare
 from test_gpu_parity import COUNTER_IMPLS, _set_impl
 from test_prune import oracle_prune
@@ -79,12 +79,38 @@ def check(crdt, D, got, want, sparse, names, skip=()):
 A_DENSE = [(D, impl) for D in (1, 3, 4, 8, 12, 17, 64, 100, 256) for impl in COUNTER_IMPLS]
 
 
-@pytest.mark.parametrize("D,impl", A_DENSE)
-def test_scan_edges_counter(eng, oracle_lib, monkeypatch, D, impl):
+def cold(case):
+    """The same requests without SCT (the cold kernels)."""
+    return (case[0], synth.cold(case[1])) + tuple(case[2:])
+
+
+def with_cold(params, ids=None, group=lambda p: p[0]):
+    """The parameter sets as they are (ids unchanged) and once more with a
+    trailing True: the cold form of the case, id + "-cold".  The cold sets of
+    a run of sets with one `group` value (one built case) follow the run."""
+    out, run = [], []
+    for j, p in enumerate(params):
+        p = p if isinstance(p, tuple) else (p,)
+        name = ids[j] if ids is not None else "-".join(str(x) for x in p)
+        if run and group(p) != group(params[j - 1] if isinstance(params[j - 1], tuple)
+                                     else (params[j - 1],)):
+            out += run
+            run = []
+        out.append(pytest.param(*p, False, id=name))
+        run.append(pytest.param(*p, True, id=name + "-cold"))
+    return out + run
+
+
+def maybe_cold(build, is_cold):
+    return (lambda: cold(build())) if is_cold else build
+
+
+@pytest.mark.parametrize("D,impl,is_cold", with_cold(A_DENSE))
+def test_scan_edges_counter(eng, oracle_lib, monkeypatch, D, impl, is_cold):
     _set_impl(monkeypatch, impl)
     crdt = _abi.COUNTER_PN
-    (log, req, _, names), want = built(oracle_lib, ("a", crdt, D, None), lambda: edges.family_a(
-        crdt, D, identity=(D % 2 == 0)), None)
+    (log, req, _, names), want = built(oracle_lib, ("a", crdt, D, None, is_cold), maybe_cold(
+        lambda: edges.family_a(crdt, D, identity=(D % 2 == 0)), is_cold), None)
     got = eng.materialize_host(log, req, sparse=False)
     check(crdt, D, got, want, None, names)
 
@@ -112,12 +138,6 @@ def presence_knobs(monkeypatch, impl):
         monkeypatch.setenv("AGN_COUNTER_IMPL", "general")
     else:
         monkeypatch.delenv("AGN_COUNTER_IMPL", raising=False)
-
-
-def cold(case):
-    """The same requests without SCT (the cold kernels)."""
-    req = dataclasses.replace(case[1], sct=None, sct_mask=None, sct_ignore=None)
-    return (case[0], req) + tuple(case[2:])
 
 
 def masked_device(eng, log, req, index, hints=0):
@@ -187,15 +207,16 @@ TAG_CASES = [(f, c, m) for f in "acd" for c in TAGS for m in TAG_MODES
              if f != "d" or c == _abi.SET_AW]
 
 
-@pytest.mark.parametrize("family,crdt,mode", TAG_CASES,
-                         ids=[f"{f}-{c}-{TAG_IDS[TAG_MODES.index(m)]}" for f, c, m in TAG_CASES])
-def test_tags_edges(eng, oracle_lib, monkeypatch, family, crdt, mode):
+@pytest.mark.parametrize("family,crdt,mode,is_cold", with_cold(
+    TAG_CASES, [f"{f}-{c}-{TAG_IDS[TAG_MODES.index(m)]}" for f, c, m in TAG_CASES],
+    group=lambda p: (p[0], p[1], p[2][0], p[2][1])))
+def test_tags_edges(eng, oracle_lib, monkeypatch, family, crdt, mode, is_cold):
     """Families A (scan edges), C (removal-token batches) and D (ops over a
-    chunk edge) through every tags shape."""
+    chunk edge) through every tags shape, with SCT arrays and without."""
     D, style, knobs = mode
     tag_knobs(monkeypatch, knobs)
-    (log, req, cap, names), want = built(oracle_lib, (family, crdt, D, style),
-                                         lambda: tags_case(family, crdt, D, style), style)
+    (log, req, cap, names), want = built(oracle_lib, (family, crdt, D, style, is_cold), maybe_cold(
+        lambda: tags_case(family, crdt, D, style), is_cold), style)
     got = eng.materialize_host(log, req, sparse=bool(style), cap_off=cap)
     check(crdt, D, got, want, style, names)
 
@@ -254,28 +275,30 @@ def check_guarded(crdt, D, got, want, style, names, cap, over=()):
         raise AssertionError(f"output slot {i} (request {r}: {names[r]}) differs")
 
 
-@pytest.mark.parametrize("crdt", TAGS)
-@pytest.mark.parametrize("mode", TAG_MODES, ids=TAG_IDS)
-def test_table_edges(eng, oracle_lib, monkeypatch, mode, crdt):
+@pytest.mark.parametrize("mode,crdt,is_cold", with_cold(
+    [(m, c) for c in TAGS for m in TAG_MODES], [f"{i}-{c}" for c in TAGS for i in TAG_IDS],
+    group=lambda p: (p[1], p[0][0], p[0][1])))
+def test_table_edges(eng, oracle_lib, monkeypatch, mode, crdt, is_cold):
     """Family B: live states on the limits of the 256- and 4096-slot tables,
     compacting churn, room one pair too small between guarded neighbours and
     more than 4096 live pairs (the engine's own limit)."""
     D, style, knobs = mode
     tag_knobs(monkeypatch, knobs)
-    (log, req, cap, names, meta), want = built(oracle_lib, ("b", crdt, D, style),
-                                               lambda: edges.family_b(crdt, D, style), style)
+    (log, req, cap, names, meta), want = built(oracle_lib, ("b", crdt, D, style, is_cold), maybe_cold(
+        lambda: edges.family_b(crdt, D, style), is_cold), style)
     over = tuple(k for k, m in meta.items() if m.get("L", 0) > edges.SLOW_CAP)
     assert len(over) == 3 and sum("room" in m for m in meta.values()) == 4
     got = guarded_run(eng, log, req, cap, style)
     check_guarded(crdt, D, got, want, style, names, cap, over)
 
 
-@pytest.mark.parametrize("crdt", TAGS)
-@pytest.mark.parametrize("D,style", [(5, None), (16, None), (8, "uniform")])
-def test_table_overflow_batch(eng, oracle_lib, crdt, D, style):
+@pytest.mark.parametrize("D,style,crdt,is_cold", with_cold(
+    [(D, st, c) for c in TAGS for D, st in [(5, None), (16, None), (8, "uniform")]],
+    group=lambda p: p))
+def test_table_overflow_batch(eng, oracle_lib, crdt, D, style, is_cold):
     """300 keys handed to the 4096-slot pass at once (its grid is 256 blocks)."""
-    (log, req, cap, names), want = built(oracle_lib, ("b300", crdt, D, style),
-                                         lambda: edges.family_b300(crdt, D, style), style)
+    (log, req, cap, names), want = built(oracle_lib, ("b300", crdt, D, style, is_cold), maybe_cold(
+        lambda: edges.family_b300(crdt, D, style), is_cold), style)
     got = guarded_run(eng, log, req, cap, style)
     check_guarded(crdt, D, got, want, style, names, cap)
 
@@ -304,13 +327,13 @@ def test_hand_on_lists_counter(eng, oracle_lib, monkeypatch, n_req, which, impl)
     check(crdt, 8, got, want, "mixed", names)
 
 
-@pytest.mark.parametrize("crdt", TAGS)
-@pytest.mark.parametrize("msk", ["1", "0"])
-def test_hand_on_lists_tags(eng, oracle_lib, monkeypatch, msk, crdt):
+@pytest.mark.parametrize("msk,crdt,is_cold", with_cold(
+    [(m, c) for c in TAGS for m in ("1", "0")], group=lambda p: p[1]))
+def test_hand_on_lists_tags(eng, oracle_lib, monkeypatch, msk, crdt, is_cold):
     """8200 masked keys, all mixed: more hand-ons than the list pass's 8192 blocks."""
     monkeypatch.setenv("AGN_TAGS_MSK", msk)
-    (log, req, cap, names), want = built(oracle_lib, ("f", crdt),
-                                         lambda: edges.family_f_tags(crdt), "mixed")
+    (log, req, cap, names), want = built(oracle_lib, ("f", crdt, is_cold), maybe_cold(
+        lambda: edges.family_f_tags(crdt), is_cold), "mixed")
     got = eng.materialize_host(log, req, sparse=True, cap_off=cap)
     check(crdt, 8, got, want, "mixed", names)
 
@@ -485,3 +508,7 @@ def test_gc_edges_oplog(eng, oracle_lib, monkeypatch, name, anchor):
         pruned = tol.pruned_log(want, n_out, crdt, D, K, sparse)
         bad = tol.materialize_view(eng, oracle_lib, view, pruned, read_all(pruned), sparse)
         assert not bad, explain(bad, names)
+        # and without SCT arrays (every type's cold form, register_lww's included)
+        bad = tol.materialize_view(eng, oracle_lib, view, pruned, synth.cold(read_all(pruned)),
+                                   sparse)
+        assert not bad, ("cold", explain(bad, names))

@@ -10,7 +10,8 @@ from antidote_amd import _abi
 from antidote_amd.encode import alloc_result, log_struct, read_struct, result_struct
 from antidote_amd.engine import Engine, free_gen_host, gen_host, host_view
 from kat_util import TYPES, OneKeyRun, kats, oracle_fn, py_ops, to_vc
-from synth import compare, random_case
+import request_space as rsp
+from synth import cold, compare, random_case
 
 pytestmark = pytest.mark.gpu
 
@@ -73,7 +74,7 @@ def test_kat_system_txn_gpu(eng, oracle_lib, c):
 # its opt-in LDS-DMA row path (glds, even D only) and the general kernel
 COUNTER_IMPLS = ("auto", "glds", "quad", "quad2", "general")
 DIFF = []
-for crdt in (_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV):
+for crdt in (_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV, _abi.REGISTER_LWW):
     for D in (1, 2, 3, 5, 8, 12, 16, 17, 33, 64, 100, 256):
         for sparse in (False, True):
             impls = COUNTER_IMPLS if crdt == _abi.COUNTER_PN else ("auto",)
@@ -117,6 +118,76 @@ def test_random_vs_oracle(eng, oracle_lib, monkeypatch, crdt, D, sparse, impl):
         ls.oc_mask = None
     assert oracle_lib.oracle_materialize(C.byref(ls), C.byref(rs), C.byref(os_), 4) == 0
     bad = compare(crdt, D, res_g, res_o, sparse, req.n_req)
+    assert not bad, bad[:10]
+
+
+_SHARED: dict = {}
+
+
+def shared_oracle(oracle_lib, key, build, sparse):
+    """(log, req, cap, oracle result) of `build`, computed once for the tests
+    that follow each other with the same key (the counter kernels)."""
+    if _SHARED.get("key") != key:
+        _SHARED.clear()
+        log, req, cap = build()
+        _SHARED.update(key=key, val=(log, req, cap, rsp.run_oracle(oracle_lib, log, req, cap, sparse)))
+    return _SHARED["val"]
+
+
+RESULT_FIELDS = ("value", "hole", "count", "flags", "err_pos", "out_n")
+
+
+@pytest.mark.parametrize("crdt,D,sparse,impl", DIFF)
+def test_random_cold_vs_oracle(eng, oracle_lib, monkeypatch, crdt, D, sparse, impl):
+    """The SCT-less templates (req.sct == NULL) on random batches: every
+    request against the oracle, and against the same requests read with the
+    SCT arrays present and every sct_ignore set -- the warm-capable template
+    on the cold template's semantics -- array by array, flags included
+    (test_oracle_crosscheck.py holds the conditions on these inputs and the
+    oracle to the same equality)."""
+    _set_impl(monkeypatch, impl)
+    assert (crdt, D, sparse) in rsp.COLD_SHAPES
+
+    def build():
+        log, req, cap = rsp.cold_case(crdt, D, sparse)
+        return log, cold(req), cap
+    log, creq, cap, want = shared_oracle(oracle_lib, ("cold", crdt, D, sparse), build, sparse)
+    got = eng.materialize_host(log, creq, sparse=sparse, cap_off=cap)
+    bad = compare(crdt, D, got, want, sparse, creq.n_req)
+    assert not bad, bad[:10]
+    ign = eng.materialize_host(log, rsp.ignore_all(rsp.cold_case(crdt, D, sparse)[1]),
+                               sparse=sparse, cap_off=cap)
+    bad = compare(crdt, D, ign, got, sparse, creq.n_req)
+    assert not bad, ("sct_ignore = 1 everywhere against sct == NULL", bad[:10])
+    # array by array where the request defines the field: all of them without
+    # an error flag, flags and err_pos always (compare above holds LastOpCt
+    # wherever F_CT_IGNORE leaves it defined)
+    ok = (want.flags & rsp.ERR) == 0
+    assert np.array_equal(ign.flags, got.flags) and np.array_equal(ign.err_pos, got.err_pos)
+    for f in RESULT_FIELDS:   # value is the counter's result, out_n the state types'
+        a, b = getattr(ign, f), getattr(got, f)
+        if a is not None and (f != "value" or crdt == _abi.COUNTER_PN):
+            assert np.array_equal(a[ok], b[ok]), f
+
+
+REKEYED = [(crdt, D, sparse, impl, warm, mode)
+           for crdt, D, sparse in rsp.REKEY_SHAPES
+           for warm in (0, 1) for mode in rsp.REKEY_MODES
+           for impl in (COUNTER_IMPLS if (crdt == _abi.COUNTER_PN and D == 8) else ("auto",))]
+
+
+@pytest.mark.parametrize("crdt,D,sparse,impl,warm,mode", REKEYED)
+def test_rekeyed_vs_oracle(eng, oracle_lib, monkeypatch, crdt, D, sparse, impl, warm, mode):
+    """Key maps that are no permutation: a third of the keys in random order,
+    and 2K + 1 requests over repeated keys -- one key in every slot of a group
+    of 8 requests, each request with its own R, SCT, txid and base
+    (synth.rekey); cold and warm."""
+    _set_impl(monkeypatch, impl)
+    log, req2, cap2, want = shared_oracle(
+        oracle_lib, ("rekey", crdt, D, sparse, warm, mode),
+        lambda: rsp.rekey_case(crdt, D, sparse, warm, mode), sparse)
+    got = eng.materialize_host(log, req2, sparse=sparse, cap_off=cap2)
+    bad = compare(crdt, D, got, want, sparse, req2.n_req)
     assert not bad, bad[:10]
 
 

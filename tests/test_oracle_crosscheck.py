@@ -14,7 +14,8 @@ import pytest
 from antidote_amd import _abi
 from antidote_amd.encode import alloc_result, log_struct, read_struct, result_struct
 from oracle import py_oracle as po
-from synth import random_case
+import request_space as rs_
+from synth import cold, random_case
 
 TYPES = {_abi.COUNTER_PN: po.COUNTER_PN, _abi.SET_AW: po.SET_AW,
          _abi.REGISTER_MV: po.REGISTER_MV, _abi.REGISTER_LWW: po.REGISTER_LWW}
@@ -80,7 +81,7 @@ def py_run(log, req, i):
     k = int(req.keys[i])
     ops = key_ops(log, k, typ)
     R = to_dict(req.R[i], req.R_mask[i] if SPARSE[0] else None, D)
-    sct = po.IGNORE if req.sct_ignore[i] else \
+    sct = po.IGNORE if req.sct is None or req.sct_ignore[i] else \
         to_dict(req.sct[i], req.sct_mask[i] if SPARSE[0] else None, D)
     txid = po.IGNORE if int(req.txid[i]) == 0 else int(req.txid[i])
     if log.crdt_type == _abi.COUNTER_PN:
@@ -142,18 +143,17 @@ for crdt in (_abi.COUNTER_PN, _abi.SET_AW, _abi.REGISTER_MV, _abi.REGISTER_LWW):
             CASES.append((crdt, D, sparse))
 
 
-@pytest.mark.parametrize("crdt,D,sparse", CASES)
-def test_c_oracle_matches_py_oracle(oracle_lib, crdt, D, sparse):
+def crosscheck(oracle_lib, log, req, cap, sparse, py_req=None):
+    """The C oracle over `req` against the py oracle over `py_req` (default: the
+    same requests), request by request."""
     SPARSE[0] = sparse
-    log, req, cap = random_case(1000 * crdt + 10 * D + sparse, crdt, 40, D, 12, sparse=sparse,
-                                warm=0.4, txid=0.3, invalid=0.03, corrupt=0.05,
-                                multi=0.2 if crdt == _abi.SET_AW else 0.0, base=0.5,
-                                identity=False)
+    py_req = req if py_req is None else py_req
+    D = log.n_dcs
     res = alloc_result(req.n_req, D, sparse=True, cap_off=cap)
     ls, rs, os_ = log_struct(log), read_struct(req, sparse=sparse), result_struct(res)
     assert oracle_lib.oracle_materialize(C.byref(ls), C.byref(rs), C.byref(os_), 2) == 0
     for i in range(req.n_req):
-        py = py_run(log, req, i)
+        py = py_run(log, py_req, i)
         c = c_decode(log, req, res, i, True)
         if py[0] == "error":
             assert c[0] == "error", (i, py, c)
@@ -164,3 +164,75 @@ def test_c_oracle_matches_py_oracle(oracle_lib, crdt, D, sparse):
             assert py[1][1] == ("invalid",)
             continue
         assert c == py, (i, c, py)
+    return res
+
+
+def crosscheck_case(crdt, D, sparse):
+    return random_case(1000 * crdt + 10 * D + sparse, crdt, 40, D, 12, sparse=sparse,
+                       warm=0.4, txid=0.3, invalid=0.03, corrupt=0.05,
+                       multi=0.2 if crdt == _abi.SET_AW else 0.0, base=0.5,
+                       identity=False)
+
+
+@pytest.mark.parametrize("crdt,D,sparse", CASES)
+def test_c_oracle_matches_py_oracle(oracle_lib, crdt, D, sparse):
+    log, req, cap = crosscheck_case(crdt, D, sparse)
+    crosscheck(oracle_lib, log, req, cap, sparse)
+
+
+@pytest.mark.parametrize("crdt,D,sparse", CASES)
+def test_c_oracle_cold_matches_py_oracle(oracle_lib, crdt, D, sparse):
+    """The C oracle's sct == NULL branch against the py oracle reading the same
+    requests with SnapshotCommitTime = ignore."""
+    log, req, cap = crosscheck_case(crdt, D, sparse)
+    assert req.sct.any() and not req.sct_ignore.all()      # there are SCT rows to drop
+    crosscheck(oracle_lib, log, cold(req), cap, sparse, py_req=rs_.ignore_all(req))
+
+
+# ------------------------------------------------------------------ cold batches of the GPU test
+@pytest.mark.parametrize("crdt,D,sparse", rs_.COLD_SHAPES)
+def test_cold_batches_meet_their_conditions(oracle_lib, crdt, D, sparse):
+    """On the inputs of test_gpu_parity.test_random_cold_vs_oracle: at least
+    half of the cold requests include an op, at most a quarter end in an error
+    flag, and the oracle gives the cold batch and the all-ignored batch the
+    same results (so the GPU test may ask the same of the kernels)."""
+    from synth import compare
+    log, req, cap = rs_.cold_case(crdt, D, sparse)
+    want = rs_.run_oracle(oracle_lib, log, cold(req), cap, sparse)
+    rs_.check_conditions(want, req.n_req)
+    ign = rs_.run_oracle(oracle_lib, log, rs_.ignore_all(req), cap, sparse)
+    assert not compare(crdt, D, ign, want, sparse, req.n_req)
+    assert np.array_equal(ign.flags, want.flags)
+    assert req.sct.any() and not req.sct_ignore.all() and req.txid.any()
+
+
+# ------------------------------------------------------------------ key maps that are no permutation
+def check_rekeyed(oracle_lib, crdt, D, sparse, warm, mode, K=40, nmax=12):
+    log, req2, cap2 = rs_.rekey_case(crdt, D, sparse, warm, mode, K=K, nmax=nmax)
+    base_req = rs_.rekey_base(crdt, D, sparse, K, nmax)[1]
+    rs_.check_rekey_properties(log, base_req, req2, mode)
+    assert (req2.sct is not None) == bool(warm)
+    crosscheck(oracle_lib, log, req2, cap2, sparse)
+
+
+@pytest.mark.parametrize("mode", rs_.REKEY_MODES)
+@pytest.mark.parametrize("warm", [0, 1], ids=["cold", "warm"])
+@pytest.mark.parametrize("crdt,D,sparse", rs_.REKEY_SHAPES)
+def test_rekeyed_c_oracle_matches_py_oracle(oracle_lib, crdt, D, sparse, warm, mode):
+    """The C oracle against the py oracle on batches whose key map is a subset
+    or repeats keys (n_req > n_keys): request i reads row i of R, SCT, txid and
+    the base arrays and key keys[i] of the log."""
+    check_rekeyed(oracle_lib, crdt, D, sparse, warm, mode)
+
+
+@pytest.mark.parametrize("crdt,D,sparse", rs_.REKEY_SHAPES)
+def test_rekeyed_gpu_batches_meet_their_conditions(oracle_lib, crdt, D, sparse):
+    """The rekeyed batches of test_gpu_parity.test_rekeyed_vs_oracle (K = 200)
+    have the stated key maps, and their requests mostly include an op."""
+    base_req = rs_.rekey_base(crdt, D, sparse, 200, 100)[1]
+    for warm in (0, 1):
+        for mode in rs_.REKEY_MODES:
+            log, req2, cap2 = rs_.rekey_case(crdt, D, sparse, warm, mode)
+            rs_.check_rekey_properties(log, base_req, req2, mode)
+            if not warm:
+                rs_.check_conditions(rs_.run_oracle(oracle_lib, log, req2, cap2, sparse), req2.n_req)
