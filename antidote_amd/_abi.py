@@ -168,6 +168,8 @@ PROTOTYPES = {
     "agn_ss_state_compact": (C.c_int, [P, C.POINTER(AgnSsCache), P, P, C.c_uint64, P]),
     "agn_read_cached": (C.c_int, [P, C.POINTER(AgnSsCache), C.POINTER(AgnLog), C.c_uint64, P, P,
                                   P, P, C.POINTER(AgnResult), P, P, P, P]),
+    "agn_read_cached_path": (C.c_int, [C.POINTER(AgnSsCache), C.POINTER(AgnLog), C.c_uint64,
+                                       C.POINTER(C.c_int)]),
     "agn_prune_ops": (C.c_int, [P, C.POINTER(AgnLog), P, P, P, C.POINTER(AgnLog), P, P, P]),
     "agn_gst_scalar": (C.c_int, [P, C.c_uint32, C.c_uint64, P, P, P]),
     "agn_oplog_create": (C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_uint32,
@@ -181,6 +183,7 @@ PROTOTYPES = {
     "agn_batcher_destroy": (C.c_int, [P]),
     "agn_batcher_read": (C.c_int, [P, C.POINTER(AgnKeyRead), C.POINTER(AgnKeyResult)]),
     "agn_batcher_stats": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "agn_batcher_path_stats": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "agn_batcher_state_bound": (C.c_int, [P, C.c_uint64, C.POINTER(C.c_uint32)]),
     "agn_batcher_store": (C.c_int, [P, C.c_uint64, P, P, C.c_int64, C.c_uint32, C.c_int64,
                                     C.c_uint32, P, P, C.c_uint32]),
@@ -233,7 +236,8 @@ ORACLE_PROTOTYPES = {
 # Additions to ABI v7 (no struct changed, the version number stayed): a library
 # built before them still loads -- an A/B against an earlier build of the same
 # ABI through AGN_LIB -- and calling a missing one raises AttributeError.
-ADDITIVE = frozenset({"agn_log_index_pack16", "agn_log_index_eff16"})
+ADDITIVE = frozenset({"agn_log_index_pack16", "agn_log_index_eff16",
+                      "agn_batcher_path_stats", "agn_read_cached_path"})
 
 
 def bind(lib, protos):

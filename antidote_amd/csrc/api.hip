@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "gen.hpp"
 #include "serve.hpp"
+#include "tags_serve.hpp"
 
 namespace agn {
 // host-staged materialize (agn_materialize_host): a non-blocking stream plus
@@ -1168,6 +1169,87 @@ static int read_cached_tags(agn_ss_cache *cache, const agn_log *log, uint64_t n_
     return rc;
 }
 
+// read/6 of a register_lww batch, D <= 64: the one fused launch
+// (tags_serve.hpp, k_lww_serve) over the caller's device arrays.  No GC list
+// and no deltas: the device state_ctl is authoritative.
+static int read_cached_lww(agn_ss_cache *cache, const agn_log *log, uint64_t n_req,
+                           const uint64_t *keys, const uint64_t *R, const uint64_t *txid,
+                           const uint8_t *should_gc, agn_result *out, uint8_t *status,
+                           uint8_t *prune, uint64_t *threshold, hipStream_t st) {
+    const uint32_t D = log->n_dcs;
+    uint8_t *tmp = nullptr;  // sct [n][D] u64 | base [n] i64 | ign [n] | first [n]
+    AGN_HIP(pool_malloc((void **)&tmp, n_req * (8ull * D + 8ull + 2ull), st));
+    agn_result o = *out;
+    o.lastct_mask = nullptr;
+    o.value = nullptr;
+    TagServe sv{};
+    sv.c = *cache;
+    sv.sct = reinterpret_cast<uint64_t *>(tmp);
+    sv.base = reinterpret_cast<int64_t *>(sv.sct + n_req * D);
+    sv.ign = reinterpret_cast<uint8_t *>(sv.base + n_req);
+    sv.first = sv.ign + n_req;
+    sv.status = status;
+    sv.gc = should_gc;
+    sv.prune = prune;
+    sv.thr = threshold;
+    agn_read rq{};
+    rq.n_req = n_req;
+    rq.keys = keys;
+    rq.R = R;
+    rq.sct = sv.sct;
+    rq.sct_ignore = sv.ign;
+    rq.txid = txid;
+    rq.req_type = log->crdt_type;
+    rq.base_value = sv.base;  // AGN_SS_STATE references into the arena
+    rq.base_tag = cache->state_tag;
+    rq.base_tok = cache->state_tok;
+    const int rc = launch_lww_serve(*log, rq, o, sv, st);
+    (void)hipFreeAsync(tmp, st);
+    return rc;
+}
+
+// register_lww's agn_read_cached batch size from which the kernel sequence
+// runs instead of the fused launch: 2^14 requests.  D = 8, keys of 64 ops,
+// hits that store nothing, fused vs sequence (scripts/ab_lww_serve.py,
+// profiles/lww_serve/ab_lww_serve*.json): 2^10 16.3 vs 25.8 us, 4096 25.6 vs
+// 27.8, 8192 38.9 vs 38.0, 12288 47.4 vs 44.9 (the sequence's runs span 43.0 to
+// 45.8), 16384 59.5 vs 51.2 (49.4 to 52.4), 2^15 105 vs 80, 2^20 3.37 vs 2.17
+// ms -- the batched lookup and store serve 8 requests per wave.  Measured at
+// D = 8 only; the one value holds for every D <= 64.
+// AGN_READ_CACHED_SPLIT=<n> moves this switch too (0: never).
+static uint64_t read_cached_lww_split() {
+    const char *v = AGN_KNOB("AGN_READ_CACHED_SPLIT");
+    if (v && v[0]) {
+        const uint64_t n = strtoull(v, nullptr, 10);
+        return n ? n : ~0ull;
+    }
+    return 1ull << 14;
+}
+
+int agn_read_cached_path(const agn_ss_cache *cache, const agn_log *log, uint64_t n_req,
+                         int *fused) {
+    int rc = check_cache(cache);
+    if (rc) return rc;
+    if (!log || !fused) return fail(AGN_EINVAL, "read_cached: null argument");
+    if (log->n_keys != cache->n_keys || log->n_dcs != cache->n_dcs)
+        return fail(AGN_EINVAL, "read_cached: log and cache disagree on keys / DCs");
+    *fused = 0;
+    if (is_pair_type(log->crdt_type)) {
+        if (!cache->state_tag || !cache->state_tok || !cache->state_ctl || cache->clock_mask)
+            return fail(AGN_ENOTSUP, "read_cached: set/register needs a cache with a state "
+                                     "arena and dense clocks");
+        if (log->crdt_type == AGN_REGISTER_LWW && lww_serve_supported(*log, false)) {
+            const char *v = AGN_KNOB("AGN_LWW_FUSED");
+            *fused = !(v && v[0] == '0') && n_req < read_cached_lww_split();
+        }
+        return AGN_OK;
+    }
+    if (!read6_supported(*log, log->n_dcs) || cache->clock_mask)
+        return fail(AGN_ENOTSUP, "read_cached: counter_pn with dense clocks, D <= 8");
+    *fused = n_req < read_cached_split(log->n_dcs);
+    return AGN_OK;
+}
+
 int agn_ss_state_compact(agn_ctx *ctx, agn_ss_cache *cache, uint32_t *new_tag, uint64_t *new_tok,
                          uint64_t new_cap, void *stream) {
     int rc = check_cache(cache);
@@ -1201,12 +1283,12 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
     int rc = check_cache(cache);
     if (rc) return rc;
     if (!log || !out || !log->key_off) return fail(AGN_EINVAL, "read_cached: null argument");
-    if (log->n_keys != cache->n_keys || log->n_dcs != cache->n_dcs)
-        return fail(AGN_EINVAL, "read_cached: log and cache disagree on keys / DCs");
+    // the validation of cache and log, and the path (one launch or the
+    // kernel sequence): agn_read_cached_path, so its answer is the dispatch
+    int fused = 0;
+    rc = agn_read_cached_path(cache, log, n_req, &fused);
+    if (rc) return rc;
     if (is_pair_type(log->crdt_type)) {
-        if (!cache->state_tag || !cache->state_tok || !cache->state_ctl || cache->clock_mask)
-            return fail(AGN_ENOTSUP, "read_cached: set/register needs a cache with a state "
-                                     "arena and dense clocks");
         if (n_req == 0) return AGN_OK;
         if (!keys || !R || !status || !prune || !threshold || !out->hole || !out->lastct ||
             !out->count || !out->flags || !out->err_pos || !out->out_off || !out->out_n ||
@@ -1214,11 +1296,12 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
             return fail(AGN_EINVAL, "read_cached: null argument");
         rc = use_device(ctx);
         if (rc) return rc;
+        if (fused)
+            return read_cached_lww(cache, log, n_req, keys, R, txid, should_gc, out, status,
+                                   prune, threshold, (hipStream_t)stream);
         return read_cached_tags(cache, log, n_req, keys, R, txid, should_gc, out, status, prune,
                                 threshold, (hipStream_t)stream);
     }
-    if (!read6_supported(*log, log->n_dcs) || cache->clock_mask)
-        return fail(AGN_ENOTSUP, "read_cached: counter_pn with dense clocks, D <= 8");
     if (n_req == 0) return AGN_OK;
     if (!keys || !R || !status || !prune || !threshold || !out->value || !out->hole ||
         !out->lastct || !out->count || !out->flags || !out->err_pos)
@@ -1226,9 +1309,8 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
     rc = use_device(ctx);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (n_req >= read_cached_split(log->n_dcs)) return read_cached_seq(cache, log, n_req, keys, R, txid,
-                                                             should_gc, out, status, prune,
-                                                             threshold, st);
+    if (!fused) return read_cached_seq(cache, log, n_req, keys, R, txid, should_gc, out, status,
+                                       prune, threshold, st);
     Read6Args a{};  // dense: the mask pointers stay null
     a.key_off = log->key_off;
     a.key_len = log->key_len;

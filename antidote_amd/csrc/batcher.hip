@@ -95,6 +95,10 @@ struct agn_batcher {
     bool cached = false;
     bool read6 = true;  // the fused one-kernel batch (AGN_READ6=0: the kernel sequence)
     bool tags_fused = true;  // set/register batches too (AGN_TAGS_FUSED=0: their sequence)
+    bool lww_fused = true;   // register_lww's fused kernel (AGN_LWW_FUSED=0: its sequence alone)
+    // agn_batcher_path_stats: batches served by one fused launch / any other way
+    std::atomic<uint64_t> n_fused{0}, n_sequence{0};
+    bool one_launch = false;  // the running batch (worker only): set by the fused paths
     agn_ss_cache ss{};
     uint64_t *thr = nullptr;    // [K][D] prune thresholds
     uint64_t *thrm = nullptr;   // [K][W] (sparse logs)
@@ -250,6 +254,7 @@ int run_batch_read6(agn_batcher *B, std::vector<Pending *> &b, bool sparse) {
         if (rc) return rc;
         rc = wait_batch(B);
         if (rc) return rc;
+        B->one_launch = true;
         bool any_prune = false;
         for (uint64_t i = 0; i < n; ++i) {
             agn_key_result *o = b[i]->out;
@@ -349,7 +354,9 @@ int ensure_state_room(agn_batcher *B, uint64_t need) {
 // from the stores' reported deltas.  A batch with keys the kernel handed on
 // (a state past the fast table, a key not uniform inside R's DC set) runs
 // the remaining passes and their store, and reads state_ctl back.
-int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse) {
+// lww: register_lww's kernel (k_lww_serve, D <= 64) over the same blocks; it
+// hands nothing on and needs no scratch words.
+int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse, bool lww) {
     const uint64_t n = b.size();
     const uint32_t D = B->D, W = B->W;
     std::vector<uint64_t> keys(n);
@@ -366,7 +373,7 @@ int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse)
         const uint64_t ncap = co[n];
         rc = ensure_state_room(B, ncap);
         if (rc) return rc;
-        if (B->tscr_n < n) {
+        if (!lww && B->tscr_n < n) {
             const uint64_t m = std::max<uint64_t>(n, 2 * B->tscr_n);
             if (B->tscr) AGN_HIP(hipFree(B->tscr));
             B->tscr = nullptr;
@@ -453,12 +460,15 @@ int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse)
         sv.dprune = (uint8_t *)(d + d_pr);
         sv.thr = B->thr;
         sv.thrm = B->thrm;
-        rc = launch_tags_serve(view, req, res, sv, B->tscr, B->stream);
+        rc = lww ? launch_lww_serve(view, req, res, sv, B->stream)
+                 : launch_tags_serve(view, req, res, sv, B->tscr, B->stream);
         if (rc) return rc;
         rc = wait_batch(B);
         if (rc) return rc;
         bool handed_on = false;
-        for (uint64_t i = 0; i < n; ++i) handed_on = handed_on || (((const uint8_t *)H(o_pr))[i] & 4u);
+        for (uint64_t i = 0; !lww && i < n; ++i)
+            handed_on = handed_on || (((const uint8_t *)H(o_pr))[i] & 4u);
+        B->one_launch = !handed_on;
         if (handed_on) {
             rc = launch_tags_serve_rest(view, req, res, sv, B->tscr, B->stream);
             if (rc) return rc;
@@ -531,7 +541,11 @@ int run_batch_cached_tags(agn_batcher *B, std::vector<Pending *> &b) {
         std::memset(&v, 0, sizeof v);
         v.n_dcs = D;
         v.crdt_type = B->crdt;
-        if (tags_serve_supported(v, sparse)) return run_batch_tags_fused(B, b, sparse);
+        if (lww_serve_supported(v, sparse)) {
+            if (B->lww_fused) return run_batch_tags_fused(B, b, sparse, true);
+        } else if (tags_serve_supported(v, sparse)) {
+            return run_batch_tags_fused(B, b, sparse, false);
+        }
     }
     std::vector<uint64_t> keys(n);
     std::vector<uint32_t> lens(n);
@@ -1083,6 +1097,7 @@ void worker_main(agn_batcher *B) {
         }
         const size_t n = batch[0]->st ? 0 : batch.size();
         lk.unlock();
+        B->one_launch = false;
         int rc = !B->cached        ? run_batch(B, batch)
                  : batch[0]->st ? run_store(B, *batch[0]->st)
                                 : run_batch_cached(B, batch);
@@ -1091,6 +1106,7 @@ void worker_main(agn_batcher *B) {
                 p->rc = rc;
                 std::snprintf(p->err, sizeof p->err, "%s", agn_last_error());
             }
+        (B->one_launch ? B->n_fused : B->n_sequence).fetch_add(1, std::memory_order_relaxed);
         B->n_batches.fetch_add(1, std::memory_order_relaxed);
         B->n_reads.fetch_add(n, std::memory_order_relaxed);
         lk.lock();
@@ -1226,6 +1242,8 @@ int agn_batcher_create_cached(agn_oplog *log, uint32_t slots, uint32_t max_batch
     (*out)->read6 = !(r6 && r6[0] == '0');
     const char *tf = AGN_KNOB("AGN_TAGS_FUSED");
     (*out)->tags_fused = !(tf && tf[0] == '0');
+    const char *lf = AGN_KNOB("AGN_LWW_FUSED");
+    (*out)->lww_fused = !(lf && lf[0] == '0');
     (*out)->ss = c;
     (*out)->thr = thr;
     (*out)->thrm = thrm;
@@ -1296,6 +1314,13 @@ int agn_batcher_stats(agn_batcher *B, uint64_t *batches, uint64_t *reads) {
     if (!B) return fail(AGN_EINVAL, "batcher_stats: null batcher");
     if (batches) *batches = B->n_batches.load();
     if (reads) *reads = B->n_reads.load();
+    return AGN_OK;
+}
+
+int agn_batcher_path_stats(agn_batcher *B, uint64_t *fused, uint64_t *sequence) {
+    if (!B) return fail(AGN_EINVAL, "batcher_path_stats: null batcher");
+    if (fused) *fused = B->n_fused.load();
+    if (sequence) *sequence = B->n_sequence.load();
     return AGN_OK;
 }
 

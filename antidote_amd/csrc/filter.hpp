@@ -70,6 +70,9 @@ struct KeyFilter {
     uint64_t txr;
     int64_t first_excl;  // position of the oldest op with notInPrev && !incl
 
+    // (init_ign below is a copy of this body: a fix here belongs there too.
+    // Forwarding to it changed the SGPR spill counts of k_counter and
+    // k_read6w, so the two stay separate.)
     __device__ __forceinline__ void init(const agn_log &log, const agn_read &req, uint64_t i) {
         lane = lane_id();
         sub = lane % LPO;
@@ -80,6 +83,36 @@ struct KeyFilter {
         grp = ((1ull << LPO) - 1ull) << (slot * LPO);
         rbits = chunk_bits<DPL, SPARSE>(req.R_mask, i, W, d0, D);
         sct_ign = req.sct == nullptr || (req.sct_ignore && req.sct_ignore[i]);
+        const uint32_t sbits =
+            sct_ign ? 0u : chunk_bits<DPL, SPARSE>(req.sct_mask, i, W, d0, D);
+#pragma unroll
+        for (int j = 0; j < DPL; ++j) {
+            const uint32_t d = (uint32_t)(d0 + j);
+            r[j] = (d < D) ? req.R[i * D + d] : 0ull;
+            s[j] = ((sbits >> j) & 1u) ? req.sct[i * D + d] : 0ull;
+            // LastOpCt starts as SnapshotCommitTime (materialize/4 :94-95)
+            ct[j] = ((sbits >> j) & 1u) ? s[j] + 1ull : 0ull;
+        }
+        txr = req.txid ? req.txid[i] : 0ull;
+        use_tx = (txr != 0ull) && (log.txid != nullptr);
+        first_excl = -1;
+    }
+
+    // init with "SCT = ignore" given by the caller (the fused cached reads: the
+    // lookup's verdict is in registers, req.sct_ignore is not read).  A copy of
+    // init's body, which stays as it is so that the kernels using it compile
+    // to what they did.
+    __device__ __forceinline__ void init_ign(const agn_log &log, const agn_read &req, uint64_t i,
+                                             bool ign) {
+        lane = lane_id();
+        sub = lane % LPO;
+        slot = lane / LPO;
+        d0 = sub * DPL;
+        D = log.n_dcs;
+        W = n_words(D);
+        grp = ((1ull << LPO) - 1ull) << (slot * LPO);
+        rbits = chunk_bits<DPL, SPARSE>(req.R_mask, i, W, d0, D);
+        sct_ign = ign;
         const uint32_t sbits =
             sct_ign ? 0u : chunk_bits<DPL, SPARSE>(req.sct_mask, i, W, d0, D);
 #pragma unroll
@@ -148,8 +181,13 @@ struct KeyFilter {
 
     // Reduce the per-lane LastOpCt accumulators across the wave (through the
     // wave's LDS stage [DPL][64]) and write lastct / lastct_mask of request i.
+    // KEEP (D <= 64: one lane per column): the row as written, and its mask
+    // word after it, also go to keep[0, DC] (the wave's LDS) for a store that
+    // follows in the same kernel.
+    template <bool KEEP = false>
     __device__ __forceinline__ void write_ct(uint64_t (*stage)[AGN_WAVE], const agn_result &out,
-                                             uint64_t i, bool ct_ign) {
+                                             uint64_t i, bool ct_ign, uint64_t *keep = nullptr) {
+        static_assert(!KEEP || S::T == 1, "KEEP: D <= 64");
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #pragma unroll
         for (int j = 0; j < DPL; ++j) stage[j][lane] = ct[j];
@@ -172,11 +210,17 @@ struct KeyFilter {
             for (int x = S::DCP; x < AGN_WAVE; x <<= 1) m = umax64(m, shfl_xor_u64(m, x));
             const bool writer = (g == 0) && ((uint32_t)c < D);
             if (writer) out.lastct[i * D + (uint32_t)c] = (m && !ct_ign) ? m - 1ull : 0ull;
+            if constexpr (KEEP) {
+                if (writer) keep[c] = (m && !ct_ign) ? m - 1ull : 0ull;
+            }
             if (SPARSE && out.lastct_mask != nullptr) {
                 const uint64_t pm = ballot(writer && m != 0ull && !ct_ign);
                 // (D in 129..192: T = 4 column groups but W = 3 mask words)
                 if (lane == 0 && (S::T == 1 || (uint32_t)t < W))
                     out.lastct_mask[i * W + (uint32_t)t] = pm;
+                if constexpr (KEEP) {
+                    if (lane == 0) keep[S::DC] = pm;
+                }
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

@@ -38,6 +38,18 @@ int launch_tags_serve(const agn_log &log, const agn_read &req, const agn_result 
 int launch_tags_serve_rest(const agn_log &log, const agn_read &req, const agn_result &out,
                            const TagServe &sv, uint32_t *scr, hipStream_t st);
 
+// The fused register_lww cached read (mat_lww.hip, k_lww_serve): lookup ->
+// k_lww's fold with the cached pair as one more candidate -> store, one wave
+// per request, one launch per batch.  A state is at most one pair and the
+// filter handles per-entry DC sets, so no request is handed on: no scratch
+// words, no _rest, and prune[i] never carries 4.  Shapes: D = 1..64, dense
+// rows or presence masks.  sv.dkeys / dprune / delta may be null (a caller
+// that keeps no GC list and reads state_ctl on the device, agn_read_cached);
+// without delta, prune[i] is bit 0 alone, as agn_ss_store writes it.
+bool lww_serve_supported(const agn_log &shape, bool sparse);
+int launch_lww_serve(const agn_log &log, const agn_read &req, const agn_result &out,
+                     const TagServe &sv, hipStream_t st);
+
 // agn_ss_store (prune flags per request) over a device list of request
 // indices list[0, *list_n) (cache.hip).
 int launch_ss_store_list(const agn_ss_cache &c, const uint64_t *key_off, const uint64_t *key_len,

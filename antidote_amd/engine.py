@@ -236,7 +236,8 @@ class Engine:
     def read_cached(self, cache, dlog, n_req, keys_ptr, R_ptr, txid_ptr, gc_ptr, dres,
                     status_ptr, prune_ptr, thr_ptr, stream=None):
         """agn_read_cached: read/6 for a batch in one kernel (ss_lookup ->
-        materialize -> ss_store), counter_pn with dense clocks, D <= 8."""
+        materialize -> ss_store): counter_pn with dense clocks, D <= 8, and
+        register_lww with a state arena, D <= 64 (read_cached_path tells)."""
         ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
         rs = dres.struct if isinstance(dres, DeviceArrays) else dres
         check(self.lib.agn_read_cached(self.ctx, C.byref(cache), C.byref(ls), n_req, keys_ptr,
@@ -571,6 +572,14 @@ class Batcher:
         check(self.lib.agn_batcher_stats(self.h, C.byref(b), C.byref(r)))
         return {"batches": b.value, "reads": r.value}
 
+    def path_stats(self):
+        """agn_batcher_path_stats: batches served by one fused launch, and
+        batches served any other way."""
+        f, s = C.c_uint64(), C.c_uint64()
+        check(self.lib.agn_batcher_path_stats(self.h, C.byref(f), C.byref(s)),
+              "agn_batcher_path_stats")
+        return {"fused": f.value, "sequence": s.value}
+
     def state_bound(self, key) -> int:
         """agn_batcher_state_bound: pairs of the largest cached state of key."""
         n = C.c_uint32()
@@ -591,6 +600,17 @@ class Batcher:
                                          int(count), int(value), n, _ptr(tg) if n else None,
                                          _ptr(tk) if n else None,
                                          _abi.READ_GC if gc else 0), "agn_batcher_store")
+
+
+def read_cached_path(cache, log, n_req) -> bool:
+    """agn_read_cached_path: whether agn_read_cached would serve these
+    arguments in one fused launch (host-only: no device is touched; raises
+    EngineError with agn_read_cached's validation codes)."""
+    ls = log.struct if isinstance(log, DeviceArrays) else log
+    fused = C.c_int(0)
+    check(load().agn_read_cached_path(C.byref(cache), C.byref(ls), n_req, C.byref(fused)),
+          "agn_read_cached_path")
+    return bool(fused.value)
 
 
 def gen_host(cfg: _abi.AgnGenCfg):

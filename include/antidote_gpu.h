@@ -598,6 +598,12 @@ int agn_batcher_create(agn_oplog *log, uint32_t max_batch, uint32_t max_wait_us,
 int agn_batcher_destroy(agn_batcher *b);
 int agn_batcher_read(agn_batcher *b, const agn_key_read *rd, agn_key_result *out);
 int agn_batcher_stats(agn_batcher *b, uint64_t *batches, uint64_t *reads);
+/* Addition to ABI v7: of those batches, *fused were served by one fused
+ * launch (cached counter_pn, set_aw / register_mv and register_lww batches
+ * in a fused shape), *sequence any other way: the kernel sequence, a
+ * set/register batch that needed its second pass, an uncached batch, an
+ * agn_batcher_store.  Either pointer may be NULL. */
+int agn_batcher_path_stats(agn_batcher *b, uint64_t *fused, uint64_t *sequence);
 /* Cached mode (counter_pn): the batcher also owns the partition's device
  * snapshot cache (an agn_ss_cache of n_keys x slots, 0 = SNAPSHOT_THRESHOLD)
  * and serves each batch as the whole of materializer_vnode:read/6
@@ -802,6 +808,21 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
                     const uint64_t *keys, const uint64_t *R, const uint64_t *txid,
                     const uint8_t *should_gc, agn_result *out, uint8_t *status, uint8_t *prune,
                     uint64_t *threshold, void *stream);
+/* register_lww (addition to ABI v7): a register_lww log over a cache with a
+ * state arena, dense clocks and D <= 64 is served by one fused launch as well
+ * (lookup -> the register_lww fold with the cached pair as one more candidate
+ * -> store, one wave per request; nothing is handed on): 16 vs 26 us for 2^10
+ * requests of 64-op keys at D = 8.  From 2^14 requests on (59 vs 51 us there,
+ * 3.37 vs 2.17 ms at 2^20; AGN_READ_CACHED_SPLIT moves this switch as well),
+ * beyond 64 DCs, or with AGN_LWW_FUSED=0, the three batched kernels.  Same
+ * results either way.
+ *
+ * agn_read_cached_path: host-only, touches no device.  *fused = 1 when
+ * agn_read_cached would serve these arguments in one launch, 0 for the
+ * batched kernels; AGN_EINVAL / AGN_ENOTSUP as agn_read_cached's validation
+ * of cache and log gives them.  agn_read_cached decides through it. */
+int agn_read_cached_path(const agn_ss_cache *cache, const agn_log *log, uint64_t n_req,
+                         int *fused);
 
 /* Re-packs the live snapshot states of a set_aw / register_mv cache into a
  * fresh arena new_tag / new_tok of new_cap pairs (device, caller-owned): every

@@ -24,11 +24,15 @@
 // type=set|register serves set_aw / register_mv partitions instead (16
 // elements / values per key; an add / assign removes / overrides the key's
 // previous token of it, as the CRDTs' downstream does): their snapshot states
-// live in the cache's device arena.
+// live in the cache's device arena.  type=lww serves register_lww partitions:
+// one {Ts, V} entry per op, no removals, a key's timestamps increasing with an
+// occasional repeat (a tie).
 //
-//   serve_bench [type=counter|set|register] [keys=N] [ops=N] [dcs=N] [present=N]
+//   serve_bench [type=counter|set|register|lww] [keys=N] [ops=N] [dcs=N] [present=N]
 //               [sparse=0|1] [parts=N] [threads=N] [reads=N] [batch=N] [wait=US]
 //               [wps=N] [hot=N] [crash=1]
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -155,6 +159,14 @@ void tag_effect(Partition &pt, uint32_t crdt, uint64_t k, uint64_t &seed, uint32
                 uint64_t &add, std::vector<uint64_t> &rems) {
     const uint64_t e = splitmix(seed) % NE;
     tag = (uint32_t)e;
+    if (crdt == AGN_REGISTER_LWW) {
+        // one {Ts, V} entry, no removals: the key's timestamps increase, now
+        // and then one repeats (a tie when its value differs)
+        uint64_t &ts = pt.last[k];
+        if (ts == 0 || splitmix(seed) % 8 != 0) ++ts;
+        add = ts;
+        return;
+    }
     add = pt.tok++;
     uint64_t &l = pt.last[crdt == AGN_SET_AW ? k * NE + e : k];
     if (l) rems.push_back(l);
@@ -192,8 +204,9 @@ int main(int argc, char **argv) {
         else if (k == "crash") crash = std::strtoull(v, nullptr, 10);
         else if (k == "type") {
             const std::string t = v;
-            crdt = t == "set" ? AGN_SET_AW : t == "register" ? AGN_REGISTER_MV : AGN_COUNTER_PN;
-            if (t != "set" && t != "register" && t != "counter") return 2;
+            crdt = t == "set" ? AGN_SET_AW : t == "register" ? AGN_REGISTER_MV
+                 : t == "lww" ? AGN_REGISTER_LWW : AGN_COUNTER_PN;
+            if (t != "set" && t != "register" && t != "lww" && t != "counter") return 2;
         }
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -381,10 +394,16 @@ int main(int argc, char **argv) {
     stop = true;
     for (auto &w : writers) w.join();
 
-    uint64_t batches = 0, breads = 0;
+    uint64_t batches = 0, breads = 0, fused = 0;  // fused: the warm-up's batches included
     for (uint64_t p = 0; p < P; ++p) {
-        uint64_t b1 = 0, r1 = 0;
+        uint64_t b1 = 0, r1 = 0, f1 = 0;
         agn_batcher_stats(parts[p].b, &b1, &r1);
+        // an addition to ABI v7, looked up so that the tool also runs against an
+        // earlier build of the library (an A/B through LD_LIBRARY_PATH)
+        using path_fn = int (*)(agn_batcher *, uint64_t *, uint64_t *);
+        static const path_fn path_stats = (path_fn)dlsym(RTLD_DEFAULT, "agn_batcher_path_stats");
+        if (path_stats) path_stats(parts[p].b, &f1, nullptr);
+        fused += f1;
         batches += b1 - b0[p];
         breads += r1 - r0[p];
     }
@@ -408,8 +427,9 @@ int main(int argc, char **argv) {
         "\"writes\": %llu, \"load_s\": %.3f, \"elapsed_s\": %.4f, \"reads_per_s\": %.1f, "
         "\"lat_us\": {\"p50\": %.1f, \"p90\": %.1f, \"p99\": %.1f, \"max\": %.1f}, "
         "\"batches\": %llu, \"mean_batch\": %.2f, \"status\": {\"hit\": %llu, \"new\": %llu, "
-        "\"log\": %llu}, \"errors\": %llu}\n",
-        crdt == AGN_SET_AW ? "set_aw" : crdt == AGN_REGISTER_MV ? "register_mv" : "counter_pn",
+        "\"log\": %llu}, \"errors\": %llu, \"fused_batches\": %llu}\n",
+        crdt == AGN_SET_AW ? "set_aw" : crdt == AGN_REGISTER_MV ? "register_mv"
+        : crdt == AGN_REGISTER_LWW ? "register_lww" : "counter_pn",
         sparse ? "sparse (presence masks, as the NIF builds it)" : "dense", (unsigned long long)present,
         (unsigned long long)P, (unsigned long long)K, (unsigned long long)H, (unsigned long long)N,
         (unsigned long long)D, (unsigned long long)T, (unsigned long long)reads,
@@ -417,7 +437,8 @@ int main(int argc, char **argv) {
         (unsigned long long)writes.load(), t_load, el, reads / el, pct(0.5), pct(0.9), pct(0.99),
         all.empty() ? 0.0 : (double)all.back(), (unsigned long long)batches,
         batches ? (double)breads / (double)batches : 0.0, (unsigned long long)hit,
-        (unsigned long long)nw, (unsigned long long)lg, (unsigned long long)er);
+        (unsigned long long)nw, (unsigned long long)lg, (unsigned long long)er,
+        (unsigned long long)fused);
     for (auto &pt : parts) {
         agn_batcher_destroy(pt.b);
         agn_oplog_destroy(pt.log);
