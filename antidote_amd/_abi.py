@@ -19,7 +19,7 @@ TAG_INVALID = 0xFFFFFFFF
 
 F_NEWSS, F_CT_IGNORE, F_ERR_UNEXPECTED, F_ERR_CORRUPTED, F_ERR_CAPACITY = 0x1, 0x2, 0x4, 0x8, 0x10
 F_CT_FULL = 0x20          # ABI v5: LastOpCt has every column (mask not written)
-F_TS_TIE = 0x40          # register_lww: another candidate has the winner's ts, another tag
+F_TS_TIE = 0x40          # register_lww: tags tied at the winner's ts, one of them unlabelled
 HINT_R_FULL, HINT_CT_FLAG, HINT_MIXED = 0x1, 0x2, 0x4
 OPS_THRESHOLD = 50  # src/materializer_vnode.erl:41
 RESIZE_THRESHOLD = 5  # :44
@@ -194,6 +194,13 @@ PROTOTYPES = {
     "agn_oplog_gc_due": (C.c_int, [P, C.c_uint64, P, P]),
     "agn_oplog_set_counter": (C.c_int, [P, C.c_uint64, P, P]),
     "agn_oplog_load": (C.c_int, [P, C.POINTER(AgnLog), P]),
+    "agn_oplog_tag_order": (C.c_int, [P, C.c_uint32, C.c_uint32, P]),
+    "agn_tagorder_create": (C.c_int, [C.POINTER(P)]),
+    "agn_tagorder_destroy": (C.c_int, [P]),
+    "agn_tagorder_size": (C.c_int, [P, C.POINTER(C.c_uint32)]),
+    "agn_tagorder_at": (C.c_int, [P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "agn_tagorder_insert": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
+    "agn_tagorder_labels": (C.c_int, [P, C.c_uint32, C.c_uint32, P]),
     "agn_interner_create": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(P)]),
     "agn_interner_destroy": (C.c_int, [P]),
     "agn_intern": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
@@ -237,7 +244,10 @@ ORACLE_PROTOTYPES = {
 # built before them still loads -- an A/B against an earlier build of the same
 # ABI through AGN_LIB -- and calling a missing one raises AttributeError.
 ADDITIVE = frozenset({"agn_log_index_pack16", "agn_log_index_eff16",
-                      "agn_batcher_path_stats", "agn_read_cached_path"})
+                      "agn_batcher_path_stats", "agn_read_cached_path",
+                      "agn_oplog_tag_order", "agn_tagorder_create", "agn_tagorder_destroy",
+                      "agn_tagorder_size", "agn_tagorder_at", "agn_tagorder_insert",
+                      "agn_tagorder_labels"})
 
 
 def bind(lib, protos):

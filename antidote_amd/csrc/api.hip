@@ -555,6 +555,24 @@ int agn_materialize(agn_ctx *ctx, const agn_log *log, const agn_read *req, agn_r
     return launch_tags(*log, *req, *out, s);
 }
 
+}  // extern "C"
+
+namespace agn {
+int materialize_ordered(agn_ctx *ctx, const agn_log *log, const agn_read *req, agn_result *out,
+                        void *stream, LwwOrder ord) {
+    if (!log || log->crdt_type != AGN_REGISTER_LWW || !ord.label)
+        return agn_materialize(ctx, log, req, out, stream);
+    int rc = validate(log, req, out);
+    if (rc) return rc;
+    rc = use_device(ctx);
+    if (rc) return rc;
+    if (req->n_req == 0) return AGN_OK;
+    return launch_lww(*log, *req, *out, (hipStream_t)stream, ord);
+}
+}  // namespace agn
+
+extern "C" {
+
 int agn_tune(agn_ctx *ctx, const agn_log *log, const agn_read *req, agn_result *out,
              void *stream, int rounds, int *choice, float *ms) {
     if (!choice) return fail(AGN_EINVAL, "tune: null choice");

@@ -460,7 +460,7 @@ int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse,
         sv.dprune = (uint8_t *)(d + d_pr);
         sv.thr = B->thr;
         sv.thrm = B->thrm;
-        rc = lww ? launch_lww_serve(view, req, res, sv, B->stream)
+        rc = lww ? launch_lww_serve(view, req, res, sv, B->stream, oplog_lww_order(B->log))
                  : launch_tags_serve(view, req, res, sv, B->tscr, B->stream);
         if (rc) return rc;
         rc = wait_batch(B);
@@ -629,7 +629,7 @@ int run_batch_cached_tags(agn_batcher *B, std::vector<Pending *> &b) {
         res.out_n = (uint32_t *)(d + o_outn);
         res.out_tag = (uint32_t *)(d + o_otag);
         res.out_tok = (uint64_t *)(d + o_otok);
-        rc = launch_tags(view, req, res, B->stream);
+        rc = launch_tags(view, req, res, B->stream, oplog_lww_order(B->log));
         if (rc) return rc;
         rc = launch_ss_store_req(B->ss, view.key_off, view.key_len, n, dkeys,
                                  (const uint8_t *)(d + o_first), (const uint8_t *)(d + o_st),
@@ -765,7 +765,7 @@ int run_batch_cached(agn_batcher *B, std::vector<Pending *> &b) {
         res.err_pos = (uint32_t *)(d + o_epos);
         // a key whose cache has no snapshot <= R (AGN_SS_LOG) still runs
         // through the kernel from the empty base; its result is discarded
-        rc = agn_materialize(B->ctx, &view, &req, &res, B->stream);
+        rc = materialize_ordered(B->ctx, &view, &req, &res, B->stream, oplog_lww_order(B->log));
         if (rc) return rc;
         // internal_store_ss / snapshot_insert_gc's policy; its prune flags go
         // per request straight into the batch's output block
@@ -932,7 +932,7 @@ int run_batch(agn_batcher *B, std::vector<Pending *> &b) {
     }
     agn_log view;
     oplog_view(B->log, &view);
-    rc = agn_materialize(B->ctx, &view, &req, &res, B->stream);
+    rc = materialize_ordered(B->ctx, &view, &req, &res, B->stream, oplog_lww_order(B->log));
     if (rc) return rc;
     AGN_HIP(hipMemcpyAsync(h + in_bytes, d + in_bytes, off - in_bytes, hipMemcpyDeviceToHost,
                            B->stream));

@@ -345,9 +345,21 @@ int launch_counter_dense(const agn_log &log, const agn_read &req, const agn_resu
                          hipStream_t s);
 int tune_counter_dense(const agn_log &log, const agn_read &req, const agn_result &out,
                        hipStream_t st, int rounds, int *choice, float *ms);
+// register_lww's value-order table (agn_oplog_tag_order): label[tag] for
+// tag < n, 0 = no label; {nullptr, 0} on every log but an engine-owned one
+// that had labels set.  Read under the log's shared hold.
+struct LwwOrder {
+    const uint64_t *label = nullptr;
+    uint32_t n = 0;
+};
+LwwOrder oplog_lww_order(const agn_oplog *L);
+// agn_materialize with the log's table (the read paths over an engine-owned log)
+int materialize_ordered(agn_ctx *ctx, const agn_log *log, const agn_read *req, agn_result *out,
+                        void *stream, LwwOrder ord);
 int launch_tags(const agn_log &log, const agn_read &req, const agn_result &out,
-                hipStream_t s);
-int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t s);
+                hipStream_t s, LwwOrder ord = LwwOrder());
+int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t s,
+               LwwOrder ord = LwwOrder());
 int launch_gst_min(uint32_t D, uint64_t P, uint64_t E, const uint64_t *clocks,
                    const uint8_t *defined, uint64_t *out, hipStream_t s);
 int launch_gst_finalize(uint32_t D, uint64_t E, uint64_t *vec, hipStream_t s);

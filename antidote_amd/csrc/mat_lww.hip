@@ -7,14 +7,21 @@
 // SURVEY.md §8(a) a5.4; parity-unpinned beyond the sequential assign).  The
 // snapshot filter is filter.hpp, the bookkeeping (NewLastOp, Count, LastOpCt,
 // the error position) that of mat_counter.hip.
-//   state = max by (ts, tag), unsigned and lexicographic, over the base pair
-//           (if any) and every included entry whose tag is valid
-//   AGN_F_TS_TIE: another candidate carries the winner's ts under another tag
-//           (tag ids are interner ids, not Erlang term order)
-// Every lane keeps the best (ts, tag) of the included ops it saw plus a "tied
-// at my best ts" bit; the wave then reduces in two steps, the u64 maximum of
-// ts and the u32 maximum of tag among the lanes at that ts, and the tie ballot
-// is the lanes at that ts whose tag differs or whose own bit is set.
+//   candidates = the base pair (if any) and every included entry whose tag is
+//           valid; wts = their largest ts, T = the distinct tags at wts
+//   state = (wts, the tag of T with the largest (label(tag), tag)), unsigned
+//           and lexicographic; label(tag) = order[tag] below the table's
+//           length, else 0 (LwwOrder: the engine-owned log's value-order
+//           table, agn_oplog_tag_order; no table: every label 0, so the
+//           largest tag id wins as it always did)
+//   AGN_F_TS_TIE: |T| > 1 and some tag of T has label 0 (tag ids are interner
+//           ids, not Erlang term order: only labels settle a tie exactly)
+// Every lane keeps the best (ts, tag) of the included ops it saw plus an
+// "unlabelled tag tied at my best ts" bit; the wave then reduces in two steps,
+// the u64 maximum of ts and the u32 maximum of tag among the lanes at that ts.
+// Only when those lanes disagree on the tag do they load their labels
+// (lww_settle, behind both reductions): a u64 maximum of the label, then the
+// u32 maximum of tag among the lanes at that label.
 //
 // ts / tag loads: a chunk's ts and tag do not depend on its verdict.  EARLY
 // issues them with the chunk's rows for every valid op (8*D + 12 bytes per op);
@@ -35,17 +42,45 @@
 namespace agn {
 namespace {
 
-// One more candidate into a lane's running maximum.
-__device__ __forceinline__ void lww_take(bool c, uint64_t ts, uint32_t tag, bool &have,
-                                         uint64_t &bts, uint32_t &btag, bool &tie) {
+__device__ __forceinline__ uint64_t lww_label(const LwwOrder &ord, uint32_t tag) {
+    return tag < ord.n ? ord.label[tag] : 0ull;
+}
+
+// Two tags at one ts (rare: two DCs assigning in the same microsecond).  Bit
+// 0: `tag` beats `btag`; bit 1: one of them has no label.
+__device__ __forceinline__ uint32_t lww_tie(const LwwOrder &ord, uint32_t tag, uint32_t btag) {
+    const uint64_t la = lww_label(ord, tag), lb = lww_label(ord, btag);
+    return ((la > lb || (la == lb && tag > btag)) ? 1u : 0u) |
+           ((la == 0ull || lb == 0ull) ? 2u : 0u);
+}
+// Out of line: the label loads and their addresses then take no register of
+// the fold loop.  k_lww's late form needs that to keep its waves per SIMD
+// (inline, <6, 1, dense, late> goes from 79 to 81 VGPRs and from six waves to
+// five).  The early form and k_lww_serve are the other way round (out of
+// line, <8, 1, dense, early> takes 4 more bytes of scratch and three serve
+// shapes lose a wave to the call's register convention), so they inline.
+__device__ __attribute__((noinline)) uint32_t lww_tie_ool(const uint64_t *label, uint32_t n,
+                                                          uint32_t tag, uint32_t btag) {
+    LwwOrder ord;
+    ord.label = label;
+    ord.n = n;
+    return lww_tie(ord, tag, btag);
+}
+
+// One more candidate into a lane's running maximum.  Labels are loaded only
+// where two tags meet at the lane's best ts; `unl`: one of them had none.
+template <bool OOL>
+__device__ __forceinline__ void lww_take(bool c, uint64_t ts, uint32_t tag, const LwwOrder &ord,
+                                         bool &have, uint64_t &bts, uint32_t &btag, bool &unl) {
     if (!c) return;
     if (!have || ts > bts) {
         bts = ts;
         btag = tag;
-        tie = false;
+        unl = false;
     } else if (ts == bts && tag != btag) {
-        tie = true;
-        btag = tag > btag ? tag : btag;
+        const uint32_t r = OOL ? lww_tie_ool(ord.label, ord.n, tag, btag) : lww_tie(ord, tag, btag);
+        unl = unl || (r & 2u) != 0u;
+        if (r & 1u) btag = tag;
     }
     have = true;
 }
@@ -65,11 +100,26 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return v;
 }
 
+// Behind the two reductions (wts, and wtag = the largest tag among the lanes
+// at wts): when those lanes disagree on the tag -- wave-uniform, rare -- each
+// loads its tag's label and the wave takes the largest (label, tag).  The
+// no-tie path loads nothing here.
+__device__ __forceinline__ void lww_settle(const LwwOrder &ord, bool at, uint32_t btag, bool unl,
+                                           uint32_t &wtag, bool &tied) {
+    tied = ballot(at && unl) != 0ull;
+    if (ballot(at && btag != wtag) != 0ull) {
+        const uint64_t lb = at ? lww_label(ord, btag) : 0ull;
+        const uint64_t wl = wave_max_u64(lb);
+        wtag = wave_max_u32((at && lb == wl) ? btag : 0u);
+        tied = tied || ballot(at && lb == 0ull) != 0ull;
+    }
+}
+
 // The one-lane-per-op shapes are held to k_counter's five waves per SIMD (96
 // VGPRs; left alone the kernel takes 100 and runs four).
 template <int DPL, int LPO, bool SPARSE, bool EARLY>
 __global__ __launch_bounds__(256, (LPO == 1 ? 5 : 1)) void k_lww(agn_log log, agn_read req,
-                                                                 agn_result out) {
+                                                                 agn_result out, LwwOrder ord) {
     using F = KeyFilter<DPL, LPO, SPARSE>;
     __shared__ uint64_t stage[4][DPL][AGN_WAVE];
     const int w = threadIdx.x >> 6;
@@ -92,7 +142,7 @@ __global__ __launch_bounds__(256, (LPO == 1 ? 5 : 1)) void k_lww(agn_log log, ag
 
         F f;
         f.init(log, req, i);
-        bool have = false, tie = false;
+        bool have = false, unl = false;
         uint64_t bts = 0;
         uint32_t btag = 0;
         uint32_t cnt = 0;
@@ -118,7 +168,7 @@ __global__ __launch_bounds__(256, (LPO == 1 ? 5 : 1)) void k_lww(agn_log log, ag
                 const uint64_t be = ballot(bad);
                 if (be) first_err = (int64_t)b + (int64_t)(__builtin_ctzll(be) / LPO);
             }
-            lww_take(lead && !bad, ts, tg, have, bts, btag, tie);
+            lww_take<!EARLY>(lead && !bad, ts, tg, ord, have, bts, btag, unl);
         }
 
         // the base state: at most one pair (the first of more), through the
@@ -134,14 +184,15 @@ __global__ __launch_bounds__(256, (LPO == 1 ? 5 : 1)) void k_lww(agn_log log, ag
                 b0 = AGN_SS_STATE_START(ref);
                 B = AGN_SS_STATE_PAIRS(ref);
             }
-            if (B != 0u) lww_take(true, req.base_tok[b0], req.base_tag[b0], have, bts, btag, tie);
+            if (B != 0u) lww_take<!EARLY>(true, req.base_tok[b0], req.base_tag[b0], ord, have, bts, btag, unl);
         }
 
         const bool any = ballot(have) != 0ull;
         const uint64_t wts = wave_max_u64(have ? bts : 0ull);
         const bool at = have && bts == wts;
-        const uint32_t wtag = wave_max_u32(at ? btag : 0u);
-        const bool tied = ballot(at && (tie || btag != wtag)) != 0ull;
+        uint32_t wtag = wave_max_u32(at ? btag : 0u);
+        bool tied;
+        lww_settle(ord, at, btag, unl, wtag, tied);
 
         const bool ct_ign = f.sct_ign && cnt == 0u;
         f.write_ct(stage[w], out, i, ct_ign);
@@ -179,17 +230,18 @@ __global__ __launch_bounds__(256, (LPO == 1 ? 5 : 1)) void k_lww(agn_log log, ag
 
 template <int DPL, int LPO, bool SPARSE, bool EARLY>
 int launch_shape(const agn_log &log, const agn_read &req, const agn_result &out,
-                 hipStream_t st) {
+                 hipStream_t st, LwwOrder ord) {
     const unsigned blocks = grid_for(req.n_req, 4, 0x7fffffffu);  // one wave per request
     hipLaunchKernelGGL((k_lww<DPL, LPO, SPARSE, EARLY>), dim3(blocks), dim3(256), 0, st, log,
-                       req, out);
+                       req, out, ord);
     AGN_HIP(hipGetLastError());
     return AGN_OK;
 }
 
 template <bool SPARSE, bool EARLY>
-int dispatch(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t st) {
-#define AGN_L(DPL, LPO) launch_shape<DPL, LPO, SPARSE, EARLY>(log, req, out, st)
+int dispatch(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t st,
+             LwwOrder ord) {
+#define AGN_L(DPL, LPO) launch_shape<DPL, LPO, SPARSE, EARLY>(log, req, out, st, ord)
     AGN_DISPATCH_SHAPES(log.n_dcs, AGN_L)
 #undef AGN_L
 }
@@ -203,7 +255,7 @@ int dispatch(const agn_log &log, const agn_read &req, const agn_result &out, hip
 // value the store branches on (hole, count, flags) is computed wave-uniformly.
 template <int DPL, int LPO, bool SPARSE>
 __global__ __launch_bounds__(256) void k_lww_serve(agn_log log, agn_read req, agn_result out,
-                                                   TagServe sv) {
+                                                   TagServe sv, LwwOrder ord) {
     using F = KeyFilter<DPL, LPO, SPARSE>;
     constexpr int DC = F::S::DC;
     static_assert(DC <= AGN_WAVE, "one lane per LastOpCt column");
@@ -257,7 +309,7 @@ __global__ __launch_bounds__(256) void k_lww_serve(agn_log log, agn_read req, ag
 
         F f;
         f.init_ign(log, req, i, lk.ign != 0);
-        bool have = false, tie = false;
+        bool have = false, unl = false;
         uint64_t bts = 0;
         uint32_t btag = 0;
         uint32_t cnt = 0;
@@ -279,20 +331,21 @@ __global__ __launch_bounds__(256) void k_lww_serve(agn_log log, agn_read req, ag
                 const uint64_t be = ballot(bad);
                 if (be) first_err = (int64_t)b + (int64_t)(__builtin_ctzll(be) / LPO);
             }
-            lww_take(lead && !bad, ts, tg, have, bts, btag, tie);
+            lww_take<false>(lead && !bad, ts, tg, ord, have, bts, btag, unl);
         }
 
         // the base state: the hit slot's pair in the arena (at most one)
         if (lane == 0 && AGN_SS_STATE_PAIRS((uint64_t)lk.base) != 0u) {
             const uint64_t b0 = AGN_SS_STATE_START((uint64_t)lk.base);
-            lww_take(true, sv.c.state_tok[b0], sv.c.state_tag[b0], have, bts, btag, tie);
+            lww_take<false>(true, sv.c.state_tok[b0], sv.c.state_tag[b0], ord, have, bts, btag, unl);
         }
 
         const bool any = ballot(have) != 0ull;
         const uint64_t wts = wave_max_u64(have ? bts : 0ull);
         const bool at = have && bts == wts;
-        const uint32_t wtag = wave_max_u32(at ? btag : 0u);
-        const bool tied = ballot(at && (tie || btag != wtag)) != 0ull;
+        uint32_t wtag = wave_max_u32(at ? btag : 0u);
+        bool tied;
+        lww_settle(ord, at, btag, unl, wtag, tied);
 
         const bool ct_ign = f.sct_ign && cnt == 0u;
         f.template write_ct<true>(stage[w], out, i, ct_ign, Sct[w]);
@@ -339,10 +392,10 @@ __global__ __launch_bounds__(256) void k_lww_serve(agn_log log, agn_read req, ag
 
 template <int DPL, int LPO, bool SPARSE>
 int serve_shape(const agn_log &log, const agn_read &req, const agn_result &out, const TagServe &sv,
-                hipStream_t st) {
+                hipStream_t st, LwwOrder ord) {
     const unsigned blocks = grid_for(req.n_req, 4, 0x7fffffffu);  // one wave per request
     hipLaunchKernelGGL((k_lww_serve<DPL, LPO, SPARSE>), dim3(blocks), dim3(256), 0, st, log, req,
-                       out, sv);
+                       out, sv, ord);
     AGN_HIP(hipGetLastError());
     return AGN_OK;
 }
@@ -350,8 +403,8 @@ int serve_shape(const agn_log &log, const agn_read &req, const agn_result &out, 
 // the AGN_DISPATCH_SHAPES rows with LPO <= 8
 template <bool SPARSE>
 int serve_dispatch(const agn_log &log, const agn_read &req, const agn_result &out,
-                   const TagServe &sv, hipStream_t st) {
-#define AGN_L(DPL, LPO) serve_shape<DPL, LPO, SPARSE>(log, req, out, sv, st)
+                   const TagServe &sv, hipStream_t st, LwwOrder ord) {
+#define AGN_L(DPL, LPO) serve_shape<DPL, LPO, SPARSE>(log, req, out, sv, st, ord)
     switch (log.n_dcs) {
         case 1: return AGN_L(1, 1);
         case 2: return AGN_L(2, 1);
@@ -376,7 +429,7 @@ bool lww_serve_supported(const agn_log &shape, bool) {
 }
 
 int launch_lww_serve(const agn_log &log, const agn_read &req, const agn_result &out,
-                     const TagServe &sv, hipStream_t st) {
+                     const TagServe &sv, hipStream_t st, LwwOrder ord) {
     if (req.n_req == 0) return AGN_OK;
     const bool sparse = log.oc_mask || req.R_mask || req.sct_mask || out.lastct_mask;
     if (!lww_serve_supported(log, sparse)) return AGN_ENOTSUP;
@@ -388,11 +441,12 @@ int launch_lww_serve(const agn_log &log, const agn_read &req, const agn_result &
     // sctm / R_mask / lastct_mask) runs the SPARSE kernel with those rows
     // null, as the sequence runs k_lww: the lookup, the filter and the store
     // read a null mask as "every DC".
-    return sparse ? serve_dispatch<true>(log, req, out, sv, st)
-                  : serve_dispatch<false>(log, req, out, sv, st);
+    return sparse ? serve_dispatch<true>(log, req, out, sv, st, ord)
+                  : serve_dispatch<false>(log, req, out, sv, st, ord);
 }
 
-int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t st) {
+int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t st,
+               LwwOrder ord) {
     if (req.n_req == 0) return AGN_OK;
     // base_value without base_off names AGN_SS_STATE references into
     // base_tag / base_tok: both arrays are required for them
@@ -404,9 +458,10 @@ int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, h
         return v && v[0] == 'l';
     }();
     const bool sparse = log.oc_mask || req.R_mask || req.sct_mask || out.lastct_mask;
-    if (late) return sparse ? dispatch<true, false>(log, req, out, st)
-                            : dispatch<false, false>(log, req, out, st);
-    return sparse ? dispatch<true, true>(log, req, out, st) : dispatch<false, true>(log, req, out, st);
+    if (late) return sparse ? dispatch<true, false>(log, req, out, st, ord)
+                            : dispatch<false, false>(log, req, out, st, ord);
+    return sparse ? dispatch<true, true>(log, req, out, st, ord)
+                  : dispatch<false, true>(log, req, out, st, ord);
 }
 
 }  // namespace agn

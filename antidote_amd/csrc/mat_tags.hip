@@ -1072,8 +1072,8 @@ int launch_tags_serve_rest(const agn_log &log, const agn_read &req, const agn_re
 }
 
 int launch_tags(const agn_log &log, const agn_read &req, const agn_result &out,
-                hipStream_t st) {
-    if (log.crdt_type == AGN_REGISTER_LWW) return launch_lww(log, req, out, st);
+                hipStream_t st, LwwOrder ord) {
+    if (log.crdt_type == AGN_REGISTER_LWW) return launch_lww(log, req, out, st, ord);
     if (req.n_req == 0) return AGN_OK;
     // base_value without base_off names AGN_SS_STATE references into
     // base_tag / base_tok (ABI v4): both arrays are required for them

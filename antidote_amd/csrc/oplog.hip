@@ -316,6 +316,10 @@ struct agn_oplog {
     uint64_t lmeta_cap = 0, list_since_sum = 0;
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
+    // register_lww: the value-order table (agn_oplog_tag_order), label by tag
+    // id, 0 = none; written under `rw` exclusive, read by kernels under it shared
+    uint64_t *order = nullptr;
+    uint32_t order_n = 0, order_cap = 0;
 
     // staging (host)
     std::vector<uint64_t> s_dst, s_tdst, s_toff, s_txid, s_add, s_oc, s_mask, s_tok;
@@ -772,7 +776,7 @@ int agn_oplog_destroy(agn_oplog *L) {
                     (void *)a.tag, (void *)a.rem_off, (void *)a.eff, (void *)a.tok,
                     (void *)L->key_off, (void *)L->key_len, (void *)L->key_id0,
                     (void *)L->key_lcap, (void *)L->key_mask, (void *)L->d_meta,
-                    (void *)L->d_lmeta})
+                    (void *)L->d_lmeta, (void *)L->order})
         if (p) (void)hipFree(p);
     if (L->pinned) (void)hipHostFree(L->pinned);
     if (L->meta) (void)hipHostFree(L->meta);
@@ -976,9 +980,50 @@ int agn_oplog_read(agn_oplog *L, const agn_read *req, agn_result *out, void *str
     if (rc) return rc;
     agn_log view;
     fill_view(L, &view);
-    rc = agn_materialize(L->ctx, &view, req, out, stream);
+    rc = materialize_ordered(L->ctx, &view, req, out, stream, oplog_lww_order(L));
     if (rc) return rc;
     AGN_HIP(hipStreamSynchronize(st));
+    return AGN_OK;
+}
+
+int agn_oplog_tag_order(agn_oplog *L, uint32_t first, uint32_t n, const uint64_t *labels) {
+    if (!L) return fail(AGN_EINVAL, "oplog_tag_order: null oplog");
+    if (L->crdt != AGN_REGISTER_LWW)
+        return fail(AGN_EINVAL, "oplog_tag_order: a log of type %u (register_lww only)", L->crdt);
+    if (n == 0) return AGN_OK;
+    if (!labels) return fail(AGN_EINVAL, "oplog_tag_order: null labels");
+    // AGN_TAG_INVALID is no value id: the table ends below it
+    if ((uint64_t)first + n > (uint64_t)AGN_TAG_INVALID)
+        return fail(AGN_EINVAL, "oplog_tag_order: ids [%u, %u + %u) past the tag id range", first,
+                    first, n);
+    int rc = use_device(L->ctx);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(L->wmu);
+    std::unique_lock<std::shared_mutex> x(L->rw);  // no read kernel is in flight
+    rc = settle(L);
+    if (rc) return rc;
+    const uint32_t end = first + n;
+    if (end > L->order_cap) {
+        uint64_t cap = std::max<uint64_t>(1024, L->order_cap);
+        while (cap < end) cap *= 2;
+        cap = std::min<uint64_t>(cap, AGN_TAG_INVALID);
+        uint64_t *t = nullptr;
+        if (hipMalloc((void **)&t, cap * 8) != hipSuccess)
+            return fail(AGN_ENOMEM, "oplog_tag_order: %llu labels", (unsigned long long)cap);
+        hipError_t e = hipMemset(t, 0, cap * 8);
+        if (e == hipSuccess && L->order_n)
+            e = hipMemcpy(t, L->order, (size_t)L->order_n * 8, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(t);
+            AGN_HIP(e);
+        }
+        if (L->order) (void)hipFree(L->order);
+        L->order = t;
+        L->order_cap = (uint32_t)cap;
+    }
+    // synchronous: the labels are in place before the lock is released
+    AGN_HIP(hipMemcpy(L->order + first, labels, (size_t)n * 8, hipMemcpyHostToDevice));
+    L->order_n = std::max(L->order_n, end);
     return AGN_OK;
 }
 
@@ -1316,6 +1361,12 @@ int oplog_begin_read(agn_oplog *L, hipStream_t st, uint64_t n, const uint64_t *k
     return AGN_OK;
 }
 void oplog_view(const agn_oplog *L, agn_log *v) { fill_view(L, v); }
+LwwOrder oplog_lww_order(const agn_oplog *L) {
+    LwwOrder o;
+    o.label = L->order;
+    o.n = L->order_n;
+    return o;
+}
 
 int oplog_prune_keys(agn_oplog *L, uint64_t n, const uint64_t *h_keys, const uint64_t *d_keys,
                      const uint8_t *d_flags, const uint64_t *thr, const uint64_t *thr_mask,

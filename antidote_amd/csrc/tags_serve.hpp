@@ -46,9 +46,11 @@ int launch_tags_serve_rest(const agn_log &log, const agn_read &req, const agn_re
 // rows or presence masks.  sv.dkeys / dprune / delta may be null (a caller
 // that keeps no GC list and reads state_ctl on the device, agn_read_cached);
 // without delta, prune[i] is bit 0 alone, as agn_ss_store writes it.
+// ord: the log's value-order table (the tie rule of mat_lww.hip); the stored
+// pair is the winner under it.
 bool lww_serve_supported(const agn_log &shape, bool sparse);
 int launch_lww_serve(const agn_log &log, const agn_read &req, const agn_result &out,
-                     const TagServe &sv, hipStream_t st);
+                     const TagServe &sv, hipStream_t st, LwwOrder ord = LwwOrder());
 
 // agn_ss_store (prune flags per request) over a device list of request
 // indices list[0, *list_n) (cache.hip).

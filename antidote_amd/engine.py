@@ -11,7 +11,7 @@ import numpy as np
 from . import _abi
 from ._lib import EngineUnavailable, check, load
 from .encode import (EncodedLog, EncodedRead, ResultArrays, alloc_result, log_struct, n_words,
-                     read_struct, result_struct)
+                     read_struct, result_struct, term_key)
 
 
 class DevBuf:
@@ -474,6 +474,13 @@ class OpLog:
         check(self.eng.lib.agn_oplog_read(self.h, C.byref(rs), C.byref(os_), stream),
               "agn_oplog_read")
 
+    def tag_order(self, first: int, labels):
+        """agn_oplog_tag_order (register_lww logs): the value-order labels of
+        tag ids [first, first + len(labels)); 0 = no label."""
+        lab = np.ascontiguousarray(np.atleast_1d(labels), np.uint64)
+        check(self.eng.lib.agn_oplog_tag_order(self.h, int(first), len(lab), _ptr(lab)),
+              "agn_oplog_tag_order")
+
     def stats(self):
         e, s, t = C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(self.eng.lib.agn_oplog_stats(self.h, C.byref(e), C.byref(s), C.byref(t)))
@@ -674,3 +681,73 @@ class Interner:
         n = C.c_uint64()
         check(self.lib.agn_interner_size(self.h, C.byref(n)))
         return n.value
+
+
+class TagOrder:
+    """agn_tagorder: the tag ids of a register_lww log's values in sorted order,
+    with a u64 label each (strictly increasing along the order) for
+    OpLog.tag_order.  The caller finds a new value's position with its own
+    comparator; insert_term does so in Erlang term order (encode.term_key).
+    Host-only."""
+
+    def __init__(self):
+        self.lib = load()
+        self.h = C.c_void_p()
+        check(self.lib.agn_tagorder_create(C.byref(self.h)), "agn_tagorder_create")
+        self._keys = {}  # tag -> sort key (insert_term)
+
+    def close(self):
+        if self.h:
+            self.lib.agn_tagorder_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        n = C.c_uint32()
+        check(self.lib.agn_tagorder_size(self.h, C.byref(n)), "agn_tagorder_size")
+        return n.value
+
+    def at(self, pos: int) -> int:
+        t = C.c_uint32()
+        check(self.lib.agn_tagorder_at(self.h, pos, C.byref(t)), "agn_tagorder_at")
+        return t.value
+
+    def insert(self, pos: int, tag: int) -> bool:
+        """-> relabelled (every label changed: upload the whole table)"""
+        r = C.c_int()
+        check(self.lib.agn_tagorder_insert(self.h, pos, tag, C.byref(r)), "agn_tagorder_insert")
+        return bool(r.value)
+
+    def labels(self, first: int, n: int) -> np.ndarray:
+        """Labels of tag ids [first, first + n), 0 = never inserted."""
+        out = np.zeros(n, np.uint64)
+        check(self.lib.agn_tagorder_labels(self.h, first, n, _ptr(out)), "agn_tagorder_labels")
+        return out
+
+    def insert_term(self, tag: int, term, oplog: "OpLog | None" = None) -> bool:
+        """Inserts `tag` at the position of its value `term` in Erlang term
+        order (encode.term_key) by binary search over the sorted tags, and
+        uploads what changed to `oplog`: the one new label, or the whole
+        table after a relabel.  -> relabelled"""
+        key = term_key(term)
+        lo, hi = 0, len(self)
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if self._keys[self.at(mid)] < key:
+                lo = mid + 1
+            else:
+                hi = mid
+        rel = self.insert(lo, tag)
+        self._keys[tag] = key
+        if oplog is not None:
+            if rel:
+                top = max(self._keys) + 1
+                oplog.tag_order(0, self.labels(0, top))
+            else:
+                oplog.tag_order(tag, self.labels(tag, 1))
+        return rel

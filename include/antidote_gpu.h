@@ -88,11 +88,19 @@ extern "C" {
  * DCs); set only for requests of a batch with AGN_HINT_CT_FLAG, and then
  * lastct_mask[i] is NOT written (the mask is the n_dcs low bits) */
 #define AGN_F_CT_FULL 0x20u
-/* register_lww (addition to ABI v7): some other candidate of the fold (base
- * pair or included entry) carries the winner's timestamp under a different
- * tag.  The device breaks the tie by the larger tag id; tag ids are interner
- * ids, not Erlang term order, so a binding that sees the flag can redo that
- * one read on the host (or intern its values in term order). */
+/* register_lww (addition to ABI v7).  The fold's candidates are the base pair
+ * (if any) and every included entry with a valid tag; wts is their largest
+ * timestamp and T the set of distinct tags at wts.  The winner is the tag of T
+ * with the largest (label(tag), tag), unsigned and lexicographic, where
+ * label(tag) is the value-order label set by agn_oplog_tag_order (0 for a tag
+ * that has none, and for every tag on a log without a table -- caller arrays,
+ * agn_materialize, agn_read_cached, a flushed view -- where the larger tag id
+ * wins).  The flag is set iff |T| > 1 and some tag of T has label 0: the tie
+ * was then not settled by labels alone.  Tag ids are interner ids, not Erlang
+ * term order; on an engine-owned log whose values are all labelled the result
+ * (and the snapshot the cached read stores) is exact and never flagged.  A
+ * binding without labels that sees the flag can redo that one read on the
+ * host (or intern its values in term order). */
 #define AGN_F_TS_TIE 0x40u
 
 /* ---- value domain ------------------------------------------------------
@@ -158,9 +166,10 @@ typedef struct agn_log {
      * `out` must carry every array the log has).  The base state and the result use the pair layout with
      * 0 or 1 pair per request (two or more base pairs: AGN_EINVAL where the
      * host sees them, on the device the first is used); out_n == 0 means
-     * Type:new().  Fold: the maximum by (ts, tag), unsigned and lexicographic,
-     * over the base pair and every included entry whose tag is valid;
-     * AGN_F_TS_TIE as defined above; an included entry with AGN_TAG_INVALID
+     * Type:new().  Fold: the largest ts over the base pair and every included
+     * entry whose tag is valid; among the tags at that ts the largest
+     * (label, tag), unsigned and lexicographic (the rule and AGN_F_TS_TIE as
+     * defined above; without labels: the largest (ts, tag)); an included entry with AGN_TAG_INVALID
      * gives AGN_F_ERR_UNEXPECTED with err_pos the oldest such entry (out_n and
      * the pair are then unspecified); one live pair and no room gives
      * AGN_F_ERR_CAPACITY with out_n = 1. */
@@ -551,6 +560,19 @@ int agn_oplog_load(agn_oplog *log, const agn_log *src, void *stream);
  * Staged appends are flushed first (read-your-writes: update/2 is a
  * sync_command that precedes the read); blocks until the kernel is done. */
 int agn_oplog_read(agn_oplog *log, const agn_read *req, agn_result *out, void *stream);
+/* Addition to ABI v7.  register_lww logs only (else AGN_EINVAL).  The
+ * value-order table: tag ids stay what they are (stable, arrival order, held
+ * in logs and cached states); the Erlang term order of the values is carried
+ * beside them as labels, order[tag] a u64 per tag id, strictly increasing in
+ * term order over the labelled values, 0 = no label.  Sets the labels of tag
+ * ids [first, first + n) from a host array; the device table grows as needed,
+ * ids never set read as 0.  Labels can be rewritten wholesale without touching
+ * a log or a cached state.  Takes the log as a flush does (exclusive against
+ * read batches); the writer calls it before appending an op that names a new
+ * value.  Seen by agn_oplog_read and by the log's batchers (the fused cached
+ * read and the kernel sequence alike); agn_oplog_flush views do not carry it,
+ * and agn_oplog_load does not copy it (the loader sets it again). */
+int agn_oplog_tag_order(agn_oplog *log, uint32_t first, uint32_t n, const uint64_t *labels);
 
 /* ---- micro-batching read queue ------------------------------------------
  * materializer_vnode:read/6 arrives per key from up to 20 read servers per
@@ -661,6 +683,28 @@ int agn_intern_find(const agn_interner *t, const void *bytes, size_t n, uint64_t
                     int *found);
 int agn_intern_bytes(const agn_interner *t, uint64_t id, const void **bytes, size_t *n);
 int agn_interner_size(const agn_interner *t, uint64_t *n);
+
+/* ---- value-order labels (register_lww; addition to ABI v7) -----------------
+ * Host-only, not thread-safe (one writer per partition).  Holds the tag ids
+ * of a log's values in sorted order and a label for each, for
+ * agn_oplog_tag_order.  The caller finds the position of a new value with its
+ * own comparator (agn_tagorder_size / _at give the sorted tags to search);
+ * the library knows nothing of Erlang terms.  Labels lie in [1, 2^64 - 2].  An
+ * insert between neighbours lo and hi takes lo + (hi - lo) / 2, a missing
+ * lower neighbour counting as 0 and a missing upper one as 2^64 - 1.  If that
+ * midpoint equals lo, every label is reassigned evenly, label_i = (i + 1) *
+ * floor((2^64 - 1) / (n + 1)) for the n tags now held in sorted position i,
+ * and *relabelled = 1 tells the caller to upload the whole table (else 0: the
+ * one new label).  agn_tagorder_labels writes the labels of tag ids [first,
+ * first + n), 0 for an id never inserted.  AGN_EINVAL, nothing changed: pos >
+ * size, a tag inserted twice, tag == AGN_TAG_INVALID, a null argument. */
+typedef struct agn_tagorder agn_tagorder;
+int agn_tagorder_create(agn_tagorder **out);
+int agn_tagorder_destroy(agn_tagorder *o);
+int agn_tagorder_size(const agn_tagorder *o, uint32_t *n);
+int agn_tagorder_at(const agn_tagorder *o, uint32_t pos, uint32_t *tag);
+int agn_tagorder_insert(agn_tagorder *o, uint32_t pos, uint32_t tag, int *relabelled);
+int agn_tagorder_labels(const agn_tagorder *o, uint32_t first, uint32_t n, uint64_t *labels);
 
 /* ---- base-snapshot selection: vector_orddict:get_smaller/2 --------------
  * (src/vector_orddict.erl:74-87, called from

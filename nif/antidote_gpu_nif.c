@@ -15,14 +15,16 @@
  *   one per vnode, holding keys of every CRDT type like ops_cache-<P>; one
  *   device op log per type, created with the type's first op; the resource's
  *   destructor frees them).  Type = a type atom (antidote_crdt_counter_pn,
- *   antidote_crdt_set_aw, antidote_crdt_register_mv) or its id 1..3:
+ *   antidote_crdt_set_aw, antidote_crdt_register_mv, antidote_crdt_register_lww)
+ *   or its id 1..4:
  *   part_open(Ctx, Type, NDcs, NKeys, Cached) -> {ok, Part}
  *       Type: the type whose log is created up front
  *   part_update(Part, Key, Type, OcPairs, TxId, Effect) -> {ok, OpId, GcDue}
  *       update/2 -> op_insert_gc/3 (agn_oplog_append): OcPairs =
  *       [{Dc, Time}] of the op's OpSSCommit, TxId a term or ignore, Effect the
  *       #clocksi_payload.op_param (counter_pn integer, set_aw
- *       [{Elem, AddToks, RemToks}], register_mv {V, Tok, Ovr} | {reset, Ovr})
+ *       [{Elem, AddToks, RemToks}], register_mv {V, Tok, Ovr} | {reset, Ovr},
+ *       register_lww {Ts, V} with integer 1 =< Ts < 2^64)
  *   part_read(Part, Key, Type, RPairs, TxId, Gc) -> {ok, Value, NewLastOp,
  *       LastOpCt, IsNewSS, Count} | {error, no_snapshot} | {error, Reason}
  *       cached partition: the whole read/6 (device snapshot cache + GC);
@@ -104,7 +106,7 @@ typedef struct {
     int ready;              /* published (release) once every field is set */
 } part_sub;
 
-#define NTYPES 4 /* indexed by AGN_COUNTER_PN .. AGN_REGISTER_MV */
+#define NTYPES 5 /* indexed by AGN_COUNTER_PN .. AGN_REGISTER_LWW */
 #define NO_HOME 0xFFu
 
 typedef struct {
@@ -112,6 +114,17 @@ typedef struct {
     part_sub sub[NTYPES];
     pthread_mutex_t sub_mu; /* creation of a type's log */
     agn_interner *keys, *dcs, *txids, *tags, *toks;
+    /* register_lww: value ids are arrival order, update/2 compares the value
+     * terms.  `vals` interns the type's values (ids dense from 0: its log's
+     * tag ids), `order` holds them sorted by enif_compare with a label each,
+     * and the labels go to the type's log (agn_oplog_tag_order) before an op
+     * that names a new value is appended: the device then settles equal
+     * timestamps in term order.  order_dirty: an upload failed, the next one
+     * sends the whole table.  One writer (the vnode); ord_mu for part_store. */
+    agn_interner *vals;
+    agn_tagorder *order;
+    int order_dirty;
+    pthread_mutex_t ord_mu;
     uint32_t type, D, W;    /* type: the one part_open created */
     uint64_t K;
     int cached;
@@ -144,6 +157,7 @@ static const char *type_name(uint32_t type) {
         case AGN_COUNTER_PN: return "antidote_crdt_counter_pn";
         case AGN_SET_AW: return "antidote_crdt_set_aw";
         case AGN_REGISTER_MV: return "antidote_crdt_register_mv";
+        case AGN_REGISTER_LWW: return "antidote_crdt_register_lww";
     }
     return "undefined";
 }
@@ -223,6 +237,9 @@ static void part_dtor(ErlNifEnv *env, void *obj) {
     agn_interner_destroy(p->txids);
     agn_interner_destroy(p->tags);
     agn_interner_destroy(p->toks);
+    agn_interner_destroy(p->vals);
+    agn_tagorder_destroy(p->order);
+    pthread_mutex_destroy(&p->ord_mu);
     pthread_mutex_destroy(&p->gc_mu);
     pthread_mutex_destroy(&p->sub_mu);
     for (size_t i = 0; i < p->n_inv; ++i) enif_release_binary(&p->inv[i].eff);
@@ -438,9 +455,9 @@ static int type_of(ErlNifEnv *env, ERL_NIF_TERM t, uint32_t *type) {
     unsigned v;
     if (enif_get_uint(env, t, &v)) {
         *type = v;
-        return v >= AGN_COUNTER_PN && v <= AGN_REGISTER_MV;
+        return v >= AGN_COUNTER_PN && v <= AGN_REGISTER_LWW;
     }
-    for (uint32_t x = AGN_COUNTER_PN; x <= AGN_REGISTER_MV; ++x)
+    for (uint32_t x = AGN_COUNTER_PN; x <= AGN_REGISTER_LWW; ++x)
         if (enif_is_identical(t, atom(env, type_name(x)))) {
             *type = x;
             return 1;
@@ -485,7 +502,7 @@ static int sub_make(part_res *p, uint32_t type, part_sub **out) {
  * type check over the key's ops, src/clocksi_materializer.erl:190-191)? */
 static int other_type_ops(part_res *p, uint64_t key, uint32_t type, int *out) {
     *out = 0;
-    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_MV && !*out; ++t) {
+    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW && !*out; ++t) {
         part_sub *s = t == type ? NULL : sub_get(p, t);
         uint32_t len = 0;
         if (!s) continue;
@@ -578,6 +595,7 @@ static ERL_NIF_TERM nif_part_open(ErlNifEnv *env, int argc, const ERL_NIF_TERM a
     pthread_mutex_init(&p->gc_mu, NULL);
     pthread_mutex_init(&p->sub_mu, NULL);
     pthread_mutex_init(&p->inv_mu, NULL);
+    pthread_mutex_init(&p->ord_mu, NULL);
     p->type = type;
     p->D = D;
     p->W = (D + 63) / 64;
@@ -599,6 +617,8 @@ static ERL_NIF_TERM nif_part_open(ErlNifEnv *env, int argc, const ERL_NIF_TERM a
     if (!rc) rc = agn_interner_create(1, UINT64_MAX / 2, &p->txids);
     if (!rc) rc = agn_interner_create(0, 0xFFFFFFFEull, &p->tags);
     if (!rc) rc = agn_interner_create(1, UINT64_MAX / 2, &p->toks);
+    if (!rc) rc = agn_interner_create(0, 0xFFFFFFFEull, &p->vals);
+    if (!rc) rc = agn_tagorder_create(&p->order);
     if (!rc) rc = sub_make(p, type, &s);
     if (rc) {
         ERL_NIF_TERM e = error_tuple(env, rc);
@@ -610,9 +630,69 @@ static ERL_NIF_TERM nif_part_open(ErlNifEnv *env, int argc, const ERL_NIF_TERM a
     return enif_make_tuple2(env, atom(env, "ok"), t);
 }
 
+/* register_lww: the id of a value term, labelled in term order on the type's
+ * log before the caller appends an op (or stores a state) that names it.  On
+ * the value's first intern its position among the sorted values is found by
+ * binary search with enif_compare on the decoded terms; the upload is the one
+ * new label, or the whole table after a relabel (or after a failed upload). */
+static int lww_value_id(ErlNifEnv *env, part_res *p, part_sub *sb, ERL_NIF_TERM value,
+                        uint64_t *id) {
+    int rc = term_id(env, p->vals, value, id);
+    if (rc) return rc;
+    const uint32_t tag = (uint32_t)*id;
+    pthread_mutex_lock(&p->ord_mu);
+    uint64_t lab = 0;
+    int rel = 0;
+    rc = agn_tagorder_labels(p->order, tag, 1, &lab);
+    const int fresh = !rc && lab == 0;
+    if (fresh) {  /* not labelled yet: its place among the sorted values */
+        uint32_t lo = 0, hi = 0;
+        rc = agn_tagorder_size(p->order, &hi);
+        while (!rc && lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            uint32_t t = 0;
+            rc = agn_tagorder_at(p->order, mid, &t);
+            if (rc) break;
+            if (enif_compare(id_term(env, p->vals, t), value) < 0) lo = mid + 1;
+            else hi = mid;
+        }
+        if (!rc) rc = agn_tagorder_insert(p->order, lo, tag, &rel);
+    }
+    const int whole = rel || p->order_dirty;
+    if (!rc && whole) {  /* every label moved, or an earlier upload failed */
+        uint64_t n = 0;
+        uint64_t *all = NULL;
+        rc = agn_interner_size(p->vals, &n);
+        if (!rc && !(all = enif_alloc(8 * (size_t)(n + 1)))) rc = AGN_ENOMEM;
+        if (!rc) rc = agn_tagorder_labels(p->order, 0, (uint32_t)n, all);
+        if (!rc) rc = agn_oplog_tag_order(sb->log, 0, (uint32_t)n, all);
+        if (all) enif_free(all);
+    } else if (!rc && fresh) {  /* the one new label */
+        rc = agn_tagorder_labels(p->order, tag, 1, &lab);
+        if (!rc) rc = agn_oplog_tag_order(sb->log, tag, 1, &lab);
+    }
+    if (fresh || whole) p->order_dirty = rc != 0;  /* the device lacks a label: send all next time */
+    pthread_mutex_unlock(&p->ord_mu);
+    return rc;
+}
+
+/* a register_lww state term: {0, <<>>} = new() (*has = 0) or {Ts, Value} with
+ * integer 1 =< Ts < 2^64 (*has = 1); 0 for anything else */
+static int lww_state_parse(ErlNifEnv *env, ERL_NIF_TERM st, int *has, ErlNifUInt64 *ts,
+                           ERL_NIF_TERM *value) {
+    int ar;
+    const ERL_NIF_TERM *tp;
+    ErlNifBinary b;
+    if (!enif_get_tuple(env, st, &ar, &tp) || ar != 2 || !enif_get_uint64(env, tp[0], ts)) return 0;
+    *has = *ts != 0;
+    *value = tp[1];
+    return *has || (enif_inspect_binary(env, tp[1], &b) && b.size == 0);
+}
+
 /* Entries of one effect (set_aw: one per {Elem, Add, Rem} part and per extra
- * add token; register_mv: one) into the arrays; returns the entry count or -1
- * when the effect cannot be represented (-> an invalid entry). */
+ * add token; register_mv: one; register_lww: one) into the arrays; returns the
+ * entry count, -1 when the effect cannot be represented (-> an invalid entry),
+ * or -2 with *err set when the engine failed. */
 #define MAXE 256
 #define MAXT 4096
 typedef struct {
@@ -646,12 +726,24 @@ static int push_entry(ErlNifEnv *env, part_res *p, entries *E, uint64_t tag, uin
     return 0;
 }
 
-static int effect_entries(ErlNifEnv *env, part_res *p, uint32_t type, ERL_NIF_TERM eff,
-                          entries *E) {
+static int effect_entries(ErlNifEnv *env, part_res *p, part_sub *sb, uint32_t type,
+                          ERL_NIF_TERM eff, entries *E, int *err) {
     E->n = E->nrem = 0;
     E->rem_off[0] = 0;
     int ar;
     const ERL_NIF_TERM *tp;
+    if (type == AGN_REGISTER_LWW) {
+        /* {Ts, Value}, integer 1 =< Ts < 2^64: tag = the value's id, add_tok =
+         * Ts raw, nothing removed (patch 5's table) */
+        ErlNifUInt64 ts = 0;
+        uint64_t id = 0;
+        if (!enif_get_tuple(env, eff, &ar, &tp) || ar != 2 || !enif_get_uint64(env, tp[0], &ts) ||
+            ts == 0)
+            return -1;
+        *err = lww_value_id(env, p, sb, tp[1], &id);
+        if (*err) return -2;
+        return push_entry(env, p, E, id, ts, NULL) ? -1 : 1;
+    }
     if (type == AGN_REGISTER_MV) {
         uint64_t tag = 0, tok = 0;
         if (!enif_get_tuple(env, eff, &ar, &tp)) return -1;
@@ -721,7 +813,13 @@ static ERL_NIF_TERM nif_part_update(ErlNifEnv *env, int argc, const ERL_NIF_TERM
         eff[0] = invalid ? AGN_EFFECT_INVALID : (int64_t)v;
         E->n = 0;
     } else {
-        const int ne = effect_entries(env, p, type, argv[5], E);
+        const int ne = effect_entries(env, p, sb, type, argv[5], E, &rc);
+        if (ne == -2) {
+            enif_free(E);
+            enif_free(oc);
+            enif_free(ocm);
+            return error_tuple(env, rc);
+        }
         if (ne < 0) {  /* not representable: one invalid entry (update/2 raises at read) */
             E->n = 1;
             E->nrem = 0;
@@ -816,6 +914,13 @@ static ERL_NIF_TERM state_term(ErlNifEnv *env, part_res *p, uint32_t type, uint3
     return l;
 }
 
+/* antidote_crdt_register_lww:new() = {0, <<>>} */
+static ERL_NIF_TERM lww_new(ErlNifEnv *env) {
+    ERL_NIF_TERM b;
+    enif_make_new_binary(env, 0, &b);
+    return enif_make_tuple2(env, enif_make_uint(env, 0), b);
+}
+
 static ERL_NIF_TERM read_result(ErlNifEnv *env, part_res *p, uint32_t type, uint64_t key,
                                 const agn_key_result *o, const uint64_t *ct, const uint64_t *ctm) {
     /* erlang:error(corrupted_ops_cache) (src/clocksi_materializer.erl:190-191) */
@@ -828,9 +933,18 @@ static ERL_NIF_TERM read_result(ErlNifEnv *env, part_res *p, uint32_t type, uint
                                 enif_make_tuple3(env, atom(env, "unexpected_operation"),
                                                  inv_get(env, p, key, type, o->err_pos),
                                                  atom(env, type_name(type))));
-    ERL_NIF_TERM v = type == AGN_COUNTER_PN
-                         ? enif_make_int64(env, o->value)
-                         : state_term(env, p, type, o->out_n, o->out_tag, o->out_tok);
+    /* register_lww: two values tied at the winner's timestamp and one of them
+     * has no label.  Every value is labelled before its op is appended, so
+     * this is an internal error, never a value. */
+    if (type == AGN_REGISTER_LWW && (o->flags & AGN_F_TS_TIE))
+        return enif_make_tuple2(env, atom(env, "error"), atom(env, "ts_tie"));
+    ERL_NIF_TERM v;
+    if (type == AGN_COUNTER_PN) v = enif_make_int64(env, o->value);
+    else if (type == AGN_REGISTER_LWW)
+        v = o->out_n ? enif_make_tuple2(env, enif_make_uint64(env, o->out_tok[0]),
+                                        id_term(env, p->vals, o->out_tag[0]))
+                     : lww_new(env);
+    else v = state_term(env, p, type, o->out_n, o->out_tag, o->out_tok);
     if (!v) return error_tuple(env, AGN_ENOMEM);
     ERL_NIF_TERM lct = (o->flags & AGN_F_CT_IGNORE) ? atom(env, "ignore") : clock_pairs(env, p, ct, ctm);
     ERL_NIF_TERM res[6] = {atom(env, "ok"), v, enif_make_int64(env, o->hole), lct,
@@ -842,12 +956,36 @@ static ERL_NIF_TERM read_result(ErlNifEnv *env, part_res *p, uint32_t type, uint
 /* a set_aw orddict [{Elem, [Tok]}] / register_mv [{V, Tok}] -> interned
  * (tag, token) pairs in the result layout (enif_alloc'ed; NULL when empty);
  * AGN_EINVAL for a malformed term */
-static int state_pairs(ErlNifEnv *env, part_res *p, uint32_t type, ERL_NIF_TERM st,
+static int state_pairs(ErlNifEnv *env, part_res *p, part_sub *sb, uint32_t type, ERL_NIF_TERM st,
                        uint32_t *n_out, uint32_t **tags_out, uint64_t **toks_out) {
     unsigned nl = 0;
     *n_out = 0;
     *tags_out = NULL;
     *toks_out = NULL;
+    if (type == AGN_REGISTER_LWW) {
+        /* {0, <<>>} = new(): no pair; {Ts, Value}: one pair (value id, Ts) */
+        int has = 0;
+        ErlNifUInt64 ts = 0;
+        ERL_NIF_TERM value;
+        uint64_t id = 0;
+        if (!lww_state_parse(env, st, &has, &ts, &value)) return AGN_EINVAL;
+        if (!has) return AGN_OK;
+        int rc = lww_value_id(env, p, sb, value, &id);
+        if (rc) return rc;
+        uint32_t *tg = enif_alloc(4);
+        uint64_t *tk = enif_alloc(8);
+        if (!tg || !tk) {
+            enif_free(tg);
+            enif_free(tk);
+            return AGN_ENOMEM;
+        }
+        tg[0] = (uint32_t)id;
+        tk[0] = ts;
+        *n_out = 1;
+        *tags_out = tg;
+        *toks_out = tk;
+        return AGN_OK;
+    }
     if (!enif_get_list_length(env, st, &nl)) return AGN_EINVAL;
     ERL_NIF_TERM h, t = st;
     uint32_t cap = 0;
@@ -931,9 +1069,13 @@ static ERL_NIF_TERM part_read_common(ErlNifEnv *env, part_res *p, ERL_NIF_TERM k
          * = SCT (ignore for read/6), nothing new, nothing cached */
         ERL_NIF_TERM v;
         ErlNifSInt64 b = 0;
+        int lar = 0;
+        const ERL_NIF_TERM *ltp = NULL;
         if (type == AGN_COUNTER_PN)
             v = (!enif_is_identical(base, atom(env, "undefined")) && enif_get_int64(env, base, &b))
                     ? enif_make_int64(env, b) : enif_make_int64(env, 0);
+        else if (type == AGN_REGISTER_LWW)
+            v = (!p->cached && enif_get_tuple(env, base, &lar, &ltp) && lar == 2) ? base : lww_new(env);
         else
             v = (!p->cached && enif_is_list(env, base)) ? base : enif_make_list(env, 0);
         ERL_NIF_TERM res[6] = {atom(env, "ok"), v, enif_make_int64(env, 0),
@@ -965,9 +1107,9 @@ static ERL_NIF_TERM part_read_common(ErlNifEnv *env, part_res *p, ERL_NIF_TERM k
     } else if (!p->cached) {
         /* base state pairs: set_aw orddict [{Elem, [Tok]}], register_mv [{V, Tok}]
          * (a cached partition's base state is the device snapshot cache's) */
-        const int src = state_pairs(env, p, type, base, &nb, &btag, &btok);
+        const int src = state_pairs(env, p, sb, type, base, &nb, &btag, &btok);
         if (src == AGN_EINVAL) return enif_make_badarg(env);
-        if (src) goto oom;
+        if (src) return error_tuple(env, src);  /* nothing allocated on failure */
         rd.n_base = nb;
         rd.base_tag = btag;
         rd.base_tok = btok;
@@ -1067,13 +1209,25 @@ static ERL_NIF_TERM nif_part_store(ErlNifEnv *env, int argc, const ERL_NIF_TERM 
     uint64_t *toks = NULL;
     if (type == AGN_COUNTER_PN) {
         if (!enif_get_int64(env, argv[6], &value)) return enif_make_badarg(env);
-    } else {
-        rc = state_pairs(env, p, type, argv[6], &n, &tags, &toks);
+    }
+    part_sub *sb = NULL;
+    if (type == AGN_REGISTER_LWW) {
+        /* a new value's label goes to the type's log: that log first, once
+         * the term is known to be well-formed (a malformed one is badarg and
+         * creates nothing, as for the other types) */
+        int has = 0;
+        ErlNifUInt64 ts = 0;
+        ERL_NIF_TERM value;
+        if (!lww_state_parse(env, argv[6], &has, &ts, &value)) return enif_make_badarg(env);
+        rc = sub_make(p, type, &sb);
+        if (rc) return error_tuple(env, rc);
+    }
+    if (type != AGN_COUNTER_PN) {
+        rc = state_pairs(env, p, sb, type, argv[6], &n, &tags, &toks);
         if (rc == AGN_EINVAL) return enif_make_badarg(env);
         if (rc) return error_tuple(env, rc);
     }
     const int gc = enif_is_identical(argv[7], atom(env, "true"));
-    part_sub *sb;
     rc = sub_make(p, type, &sb);
     if (!rc)
         rc = agn_batcher_store(sb->bt, k, row, mask, last_op, count, value, n, tags, toks,
@@ -1096,7 +1250,7 @@ static ERL_NIF_TERM nif_part_gc(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
     agn_ctx *c = p->ctx->ctx;
     const uint8_t one = 1;
     pthread_mutex_lock(&p->gc_mu);
-    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_MV && !rc; ++t) {
+    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW && !rc; ++t) {
         part_sub *s = sub_get(p, t);
         uint32_t len = 0;
         if (!s) continue;
@@ -1133,7 +1287,7 @@ static ERL_NIF_TERM nif_part_gc_due(ErlNifEnv *env, int argc, const ERL_NIF_TERM
     uint8_t due = 0;
     if (p->khome[k] != NO_HOME) {
         uint32_t total = 0, lcap = 0;
-        for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_MV && !rc; ++t) {
+        for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW && !rc; ++t) {
             part_sub *s = sub_get(p, t);
             uint32_t len = 0, ll = 0;
             if (!s) continue;
@@ -1152,7 +1306,7 @@ static ERL_NIF_TERM nif_part_stats(ErlNifEnv *env, int argc, const ERL_NIF_TERM 
     part_res *p;
     uint64_t E = 0, S = 0, T = 0;
     if (argc != 1 || !get_part(env, argv[0], &p)) return enif_make_badarg(env);
-    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_MV; ++t) {
+    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW; ++t) {
         part_sub *s = sub_get(p, t);
         uint64_t e, sl, tk;
         if (!s) continue;

@@ -27,6 +27,7 @@
 -define(COUNTER, 1).
 -define(SET_AW, 2).
 -define(REGISTER_MV, 3).
+-define(REGISTER_LWW, 4).
 -define(F_NEWSS, 1).
 -define(F_CT_IGNORE, 2).
 -define(F_ERR_UNEXPECTED, 4).
@@ -66,7 +67,8 @@ ctx() ->
 
 type_id(antidote_crdt_counter_pn) -> ?COUNTER;
 type_id(antidote_crdt_set_aw) -> ?SET_AW;
-type_id(antidote_crdt_register_mv) -> ?REGISTER_MV.
+type_id(antidote_crdt_register_mv) -> ?REGISTER_MV;
+type_id(antidote_crdt_register_lww) -> ?REGISTER_LWW.
 
 %% ---------------------------------------------------------------------------
 %% clocksi_materializer:materialize/4, same arguments and results.
@@ -79,7 +81,7 @@ materialize(Type, TxId, MinSnapshotTime,
     D = max(1, length(Dcs)),
     Idx = maps:from_list(lists:zip(Dcs, lists:seq(0, length(Dcs) - 1))),
     TxCodes = txid_codes(TxId, OpList),
-    {Log, Terms, Tags0, Toks0} = encode_log(Type, TypeId, OpList, Idx, D, TxCodes),
+    {Log, Terms, Tags0, Toks0} = encode_log(Type, TypeId, OpList, Idx, D, TxCodes, Base),
     {BaseOff, BaseTag, BaseTok, Tags, Toks} = encode_base(TypeId, Base, Tags0, Toks0),
     {Read, CapOff} = encode_read(TypeId, Idx, D, MinSnapshotTime, SCT, txid_code(TxId, TxCodes),
                                  Base, {BaseOff, BaseTag, BaseTok}, Log),
@@ -149,7 +151,7 @@ txid_codes(TxId, OpList) ->
                            end, {#{}, 1}, All),
     Map.
 
-encode_log(Type, TypeId, OpList, Idx, D, TxCodes) ->
+encode_log(Type, TypeId, OpList, Idx, D, TxCodes, BaseState) ->
     KeyType = case lists:all(fun({_, #clocksi_payload{type = T}}) -> T =:= Type end, OpList) of
                   true -> TypeId;
                   false -> 16#FF
@@ -177,15 +179,32 @@ encode_log(Type, TypeId, OpList, Idx, D, TxCodes) ->
         _ ->
             %% one entry per {Elem, Add, Rem} part (add_all / remove_all) and
             %% per extra add token, all under the op's id
-            encode_tag_log(KeyType, OpList, TypeId, Idx, D, TxCodes)
+            encode_tag_log(KeyType, OpList, TypeId, Idx, D, TxCodes, BaseState)
     end.
 
 txid_code(ignore, _) -> 0;
 txid_code(T, Codes) -> maps:get(T, Codes).
 
-encode_tag_log(KeyType, OpList, TypeId, Idx, D, TxCodes) ->
-    %% entries: {OpId, Op, TagTerm | invalid, AddTok | none, Rems}
+encode_tag_log(KeyType, OpList, TypeId, Idx, D, TxCodes, BaseState) ->
+    %% entries: {OpId, Op, TagTerm | invalid, AddTok | none | {raw, Ts}, Rems}
     Entries = lists:append([op_entries(TypeId, Id, Op) || {Id, Op} <- OpList]),
+    %% register_lww: update/2 is max(Effect, State) over {Ts, Value} in term
+    %% order and the device breaks equal timestamps by the value id, so the
+    %% call's values (the base state's included) are interned in term order
+    %% first: ids then follow it, and no read of this call can come back with
+    %% AGN_F_TS_TIE settled the wrong way.  lists:sort/1, not usort/1: usort
+    %% merges with ==, the intern map matches exactly, so of 1 and 1.0 one
+    %% would be dropped here and interned later, out of order; sorted, the two
+    %% take neighbouring ids (intern/2 drops the exact duplicates)
+    Tags00 = case TypeId of
+                 ?REGISTER_LWW ->
+                     SortedVals = lists:sort([LogV || {_, _, LogV, {raw, _}, _} <- Entries] ++
+                                                 [BaseV || {BaseTs, BaseV} <- [BaseState],
+                                                           BaseTs =/= 0]),
+                     lists:foldl(fun(SV, Acc) -> {Acc1, _} = intern(SV, Acc), Acc1 end, #{},
+                                 SortedVals);
+                 _ -> #{}
+             end,
     N = length(Entries),
     {Rows, Masks} = lists:unzip([row(clock_of(Op), Idx, D) || {_, Op, _, _, _} <- Entries]),
     Ids = << <<Id:32/native>> || {Id, _, _, _, _} <- Entries >>,
@@ -196,13 +215,17 @@ encode_tag_log(KeyType, OpList, TypeId, Idx, D, TxCodes) ->
                  [hd(OffA0) | OffA0], RemA0, maps:put(I, Op#clocksi_payload.op_param, Tm), I + 1};
            ({_, _, TagTerm, AddTok, Rems}, {Tg, Tk, TagA0, AddA0, OffA0, RemA0, Tm, I}) ->
                 {Tg1, TagId} = intern(TagTerm, Tg),
-                {Tk1, AddId} = case AddTok of none -> {Tk, 0}; _ -> intern(AddTok, Tk) end,
+                {Tk1, AddId} = case AddTok of
+                                   none -> {Tk, 0};
+                                   {raw, Ts} -> {Tk, Ts};       % register_lww: Ts itself
+                                   _ -> intern(AddTok, Tk)
+                               end,
                 {Tk2, RemIds} = lists:foldl(fun(X, {T, L}) -> {T2, Id} = intern(X, T), {T2, [Id | L]} end,
                                             {Tk1, []}, Rems),
                 Off = hd(OffA0) + length(RemIds),
                 {Tg1, Tk2, [<<TagId:32/native>> | TagA0], [<<AddId:64/native>> | AddA0],
                  [Off | OffA0], [[<<R:64/native>> || R <- lists:reverse(RemIds)] | RemA0], Tm, I + 1}
-        end, {#{}, #{}, [], [], [0], [], #{}, 0}, Entries),
+        end, {Tags00, #{}, [], [], [0], [], #{}, 0}, Entries),
     Log = {<<0:64/native, N:64/native>>, <<KeyType:8>>, iolist_to_binary(Rows),
            iolist_to_binary(Masks), Ids, TxIds, <<>>,
            iolist_to_binary(lists:reverse(TagA)), iolist_to_binary(lists:reverse(AddA)),
@@ -226,6 +249,8 @@ parts(?SET_AW, Parts) when is_list(Parts) ->
     end;
 parts(?REGISTER_MV, {reset, Ovr}) when is_list(Ovr) -> {ok, [{reset, none, Ovr}]};
 parts(?REGISTER_MV, {Value, Token, Ovr}) when is_list(Ovr) -> {ok, [{Value, Token, Ovr}]};
+parts(?REGISTER_LWW, {Ts, Value}) when is_integer(Ts), Ts >= 1, Ts =< ?U64_MAX ->
+    {ok, [{Value, {raw, Ts}, []}]};
 parts(_, _) -> error.
 
 set_part({Elem, [], Rems}) when is_list(Rems) -> [{Elem, none, Rems}];
@@ -239,6 +264,11 @@ encode_base(?SET_AW, State, Tags, Toks) ->
     base_pairs([{E, T} || {E, Ts} <- State, T <- Ts], Tags, Toks);
 encode_base(?REGISTER_MV, State, Tags, Toks) ->
     base_pairs(State, Tags, Toks);
+encode_base(?REGISTER_LWW, {0, _}, Tags, Toks) ->       % new() = {0, <<>>}: no pair
+    {<<0:64/native, 0:64/native>>, <<>>, <<>>, Tags, Toks};
+encode_base(?REGISTER_LWW, {Ts, Value}, Tags, Toks) ->  % interned with the log's values
+    {<<0:64/native, 1:64/native>>, <<(maps:get(Value, Tags)):32/native>>, <<Ts:64/native>>,
+     Tags, Toks};
 encode_base(_, _, Tags, Toks) ->
     {<<>>, <<>>, <<>>, Tags, Toks}.
 
@@ -293,6 +323,7 @@ decode(Type, TypeId, Dcs, D, {Value, Hole, LastCt, LastCtMask, Count, Flags, Err
                  end,
             V = case TypeId of
                     ?COUNTER -> <<X:64/signed-native>> = Value, X;
+                    ?REGISTER_LWW -> decode_lww(OutN, OutTag, OutTok, Tags);
                     _ -> decode_state(TypeId, OutN, OutTag, OutTok, Tags, Toks)
                 end,
             {ok, V, H, Ct, F band ?F_NEWSS =/= 0, C}
@@ -317,6 +348,12 @@ decode_state(TypeId, <<N:32/native>>, TagBin, TokBin, Tags, Toks) ->
                                           end, [], Terms));
         ?REGISTER_MV -> lists:sort(Terms)
     end.
+
+%% register_lww: the one pair {value id, Ts}, or new()
+decode_lww(<<0:32/native>>, _, _, _) -> {0, <<>>};
+decode_lww(<<1:32/native>>, <<T:32/native, _/binary>>, <<Ts:64/native, _/binary>>, Tags) ->
+    [Value] = [V || {V, I} <- maps:to_list(Tags), I =:= T],
+    {Ts, Value}.
 
 %% ---------------------------------------------------------------------------
 %% stable_time_functions:get_min_time/1 on the device.

@@ -100,6 +100,7 @@ def main():
     print(json.dumps({
         "keys": K, "ops_per_key": N, "D": D, "rounds": rounds, "included_fraction": incl,
         "ms_median": med, "ms_min": {n: float(min(x)) for n, x in ms.items()},
+        "ms_max": {n: float(max(x)) for n, x in ms.items()},
         "bytes_per_op": per_op,
         "hbm_fraction_of_8TBs": {n: byts[n] / (med[n] * 1e-3) / PEAK for n in names},
         "vs_counter_general": {n: med[n] / base for n in names},
