@@ -13,6 +13,8 @@ OK = 0
 EINVAL, EHIP, ENOMEM, ECAPACITY, ENOTSUP, ERCCL, ENODEV = -1, -2, -3, -4, -5, -6, -7
 
 COUNTER_PN, SET_AW, REGISTER_MV, REGISTER_LWW = 1, 2, 3, 4
+COUNTER_B = 6  # 5 is reserved (refused)
+BCOUNTER_SLOTS_MAX = 256
 TYPE_MIXED = 0xFF
 EFFECT_INVALID = -(1 << 63)
 TAG_INVALID = 0xFFFFFFFF
@@ -32,6 +34,7 @@ TYPE_NAMES = {
     SET_AW: "antidote_crdt_set_aw",
     REGISTER_MV: "antidote_crdt_register_mv",
     REGISTER_LWW: "antidote_crdt_register_lww",
+    COUNTER_B: "antidote_crdt_counter_b",
 }
 TYPE_IDS = {v: k for k, v in TYPE_NAMES.items()}
 

@@ -18,11 +18,11 @@ from __future__ import annotations
 from . import _abi
 from .encode import (IGNORE, ClocksiPayload, DcTable, LogEncoder, ReadEncoder, decode_clock,
                      term_key)
-from .records import (COUNTER_PN, REGISTER_LWW, REGISTER_MV, SET_AW, CorruptedOpsCache,
+from .records import (COUNTER_B, COUNTER_PN, REGISTER_LWW, REGISTER_MV, SET_AW, CorruptedOpsCache,
                       MaterializedSnapshot, SnapshotGetResponse, ops_oldest_first)
 
 _TYPE_IDS = {COUNTER_PN: _abi.COUNTER_PN, SET_AW: _abi.SET_AW, REGISTER_MV: _abi.REGISTER_MV,
-             REGISTER_LWW: _abi.REGISTER_LWW}
+             REGISTER_LWW: _abi.REGISTER_LWW, COUNTER_B: _abi.COUNTER_B}
 LWW_NEW = (0, b"")  # antidote_crdt_register_lww:new() = {0, <<>>}
 _engines: dict = {}
 
@@ -47,12 +47,14 @@ def new(typ: str):
     type_id(typ)
     if typ == REGISTER_LWW:
         return LWW_NEW
+    if typ == COUNTER_B:      # antidote_crdt_counter_b:new() = {[], []}
+        return ([], [])
     return 0 if typ == COUNTER_PN else []
 
 
 def value(typ: str, state):
     """Type:value/1."""
-    if typ == COUNTER_PN:
+    if typ in (COUNTER_PN, COUNTER_B):
         return state
     if typ == SET_AW:
         return [e for e, _ in state]
@@ -77,6 +79,9 @@ def _base_pairs(typ, snapshot):
     if typ == REGISTER_LWW:   # {Ts, Value}: no pair for new(), else (value, ts)
         ts, v = snapshot
         return [] if (ts, v) == LWW_NEW else [(v, ts)]
+    if typ == COUNTER_B:      # {P, D}: one pair per orddict key, the slot terms of the encoder
+        P, D = snapshot
+        return [(("P", k), v) for k, v in P] + [(("D", k), v) for k, v in D]
     return [(v, t) for v, t in snapshot]
 
 
@@ -101,6 +106,14 @@ def _decode_state(typ, enc, res, i):
     o, n = int(res.out_off[i]), int(res.out_n[i])
     if typ == REGISTER_LWW:   # out_n == 0: Type:new()
         return (int(res.out_tok[o]), enc.tags.term(int(res.out_tag[o]))) if n else LWW_NEW
+    if typ == COUNTER_B:      # pairs -> {P, D}, each an orddict in term order
+        P, D = [], []
+        for t, k in zip(res.out_tag[o:o + n], res.out_tok[o:o + n]):
+            kind, key = enc.tags.term(int(t))
+            v = int(k) - (1 << 64) if int(k) >> 63 else int(k)
+            (P if kind == "P" else D).append((key, v))
+        return (sorted(P, key=lambda kv: term_key(kv[0])),
+                sorted(D, key=lambda kv: term_key(kv[0])))
     pairs = [(enc.tags.term(int(t)), enc.tokens.term(int(k)))
              for t, k in zip(res.out_tag[o:o + n], res.out_tok[o:o + n])]
     if typ == SET_AW:
@@ -109,6 +122,21 @@ def _decode_state(typ, enc, res, i):
             st.setdefault(e, []).append(tk)
         return sorted(st.items(), key=lambda kv: kv[0])   # orddict by elem term
     return sorted(pairs)              # insert_sorted({Value, Token})
+
+
+def permissions(state) -> int:
+    """antidote_crdt_counter_b:permissions/1: the {I, I} entries of P less D."""
+    P, D = state
+    return sum(v for (a, b), v in P if a == b) - sum(v for _, v in D)
+
+
+def local_permissions(ident, state) -> int:
+    """antidote_crdt_counter_b:localPermissions/2: received (own increments
+    included) less granted less the id's decrements."""
+    P, D = state
+    received = sum(v for (_, to), v in P if to == ident)
+    granted = sum(v for (frm, to), v in P if frm == ident and to != ident)
+    return received - granted - sum(v for i, v in D if i == ident)
 
 
 def materialize_batch(typ: str, reads, device: int = 0):

@@ -165,8 +165,13 @@ hipError_t pool_malloc(void **p, size_t bytes, hipStream_t st) {
 static bool is_tag_type(uint32_t t) { return t == AGN_SET_AW || t == AGN_REGISTER_MV; }
 // The types whose log entries, base state and result use the tag-type / pair
 // layout: the tag types plus register_lww (tag = value id, tok = timestamp,
-// no removals, at most one pair).
-static bool is_pair_type(uint32_t t) { return is_tag_type(t) || t == AGN_REGISTER_LWW; }
+// no removals, at most one pair) and counter_b (tag = slot id, tok = the
+// amount / sum, no removals; add_tok == 0 is a value there, not "no add").
+static bool is_pair_type(uint32_t t) {
+    return is_tag_type(t) || t == AGN_REGISTER_LWW || t == AGN_COUNTER_B;
+}
+// The pair types without removals: rem_off / rem_tok are not read by a read.
+static bool is_norem_type(uint32_t t) { return t == AGN_REGISTER_LWW || t == AGN_COUNTER_B; }
 
 // A log whose key_mask agn_log_index_masks built (same buffer, same key
 // count) with many mixed keys (many_mixed).
@@ -377,12 +382,13 @@ static int validate(const agn_log *log, const agn_read *req, const agn_result *o
     if (log->crdt_type == AGN_COUNTER_PN) {
         if (log->n_entries && !log->eff) return fail(AGN_EINVAL, "counter_pn log needs eff");
         if (!out->value) return fail(AGN_EINVAL, "counter_pn result needs value");
-    } else if (log->crdt_type == AGN_REGISTER_LWW) {
+    } else if (is_norem_type(log->crdt_type)) {
         // no removals: rem_off / rem_tok are not read for the type
+        const char *nm = log->crdt_type == AGN_COUNTER_B ? "counter_b" : "register_lww";
         if (log->n_entries && (!log->tag || !log->add_tok))
-            return fail(AGN_EINVAL, "register_lww log needs tag/add_tok");
+            return fail(AGN_EINVAL, "%s log needs tag/add_tok", nm);
         if (!out->out_off || !out->out_n || !out->out_tag || !out->out_tok)
-            return fail(AGN_EINVAL, "register_lww result needs out_off/out_n/out_tag/out_tok");
+            return fail(AGN_EINVAL, "%s result needs out_off/out_n/out_tag/out_tok", nm);
     } else {
         if (log->n_entries && (!log->tag || !log->add_tok || !log->rem_off))
             return fail(AGN_EINVAL, "set/register log needs tag/add_tok/rem_off");
@@ -730,6 +736,15 @@ int agn_state_capacity(const agn_log *log, const agn_read *req, uint64_t *cap_of
                 return fail(AGN_EINVAL, "register_lww: request %llu has %llu base pairs",
                             (unsigned long long)i, (unsigned long long)b);
             cap_off[i + 1] = cap_off[i] + ((b || key_n(log->key_off, log->key_len, k)) ? 1 : 0);
+            continue;
+        }
+        if (log->crdt_type == AGN_COUNTER_B) {
+            // every entry may name a slot of its own, whatever its amount
+            // (0 is a value): the key's entries + the base pairs
+            c = key_n(log->key_off, log->key_len, k);
+            if (req->base_off) c += req->base_off[i + 1] - req->base_off[i];
+            else if (req->base_value) c += AGN_SS_STATE_PAIRS(req->base_value[i]);
+            cap_off[i + 1] = cap_off[i] + c;
             continue;
         }
         if (log->add_tok)

@@ -92,6 +92,13 @@ __device__ inline int64_t wave_sum_i64(int64_t v) {
 
 __device__ inline uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
+// LDS written by one lane of a wave is read by others after this (k_tags'
+// candidate table, k_bcounter's slot table).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // Bit g of the result = some bit of group g (P consecutive bits) of the wave
 // ballot b, on the scalar unit: the per-op verdict of a ballot whose P lanes
 // per op hold its P 16-byte parts.
@@ -360,6 +367,9 @@ int launch_tags(const agn_log &log, const agn_read &req, const agn_result &out,
                 hipStream_t s, LwwOrder ord = LwwOrder());
 int launch_lww(const agn_log &log, const agn_read &req, const agn_result &out, hipStream_t s,
                LwwOrder ord = LwwOrder());
+// counter_b (mat_bcounter.hip): the group-by-sum fold; launch_tags routes to it
+int launch_bcounter(const agn_log &log, const agn_read &req, const agn_result &out,
+                    hipStream_t s);
 int launch_gst_min(uint32_t D, uint64_t P, uint64_t E, const uint64_t *clocks,
                    const uint8_t *defined, uint64_t *out, hipStream_t s);
 int launch_gst_finalize(uint32_t D, uint64_t E, uint64_t *vec, hipStream_t s);

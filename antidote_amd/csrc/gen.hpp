@@ -127,6 +127,16 @@ AGN_HD inline void gen_key(const agn_gen_cfg &cfg, uint64_t k, GenOut &o) {
             }
             continue;
         }
+        if (cfg.crdt_type == AGN_COUNTER_B) {
+            // a slot of n_elems and a small signed amount (0 included)
+            const uint32_t sl = (uint32_t)rng.uni(0, E - 1);
+            const int64_t amt = (int64_t)rng.uni(0, 2000) - 1000;
+            if (write) {
+                o.tag[i] = sl;
+                o.add_tok[i] = (uint64_t)amt;
+            }
+            continue;
+        }
         const uint64_t tok = (gk << 24) | (uint64_t)(i + 1);
         uint32_t tag = 0;
         uint64_t add = 0;

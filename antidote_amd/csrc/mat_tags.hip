@@ -74,11 +74,6 @@ __device__ __forceinline__ uint32_t chain_next(const CandLds<CAP> &L, uint32_t x
     return v == 0xffffu ? NIL : v;
 }
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __device__ __forceinline__ uint64_t lanes_below() {
     const int lane = lane_id();
     return lane == 0 ? 0ull : (~0ull >> (64 - lane));
@@ -1034,6 +1029,7 @@ int serve_dispatch(const agn_log &log, const agn_read &req, const agn_result &ou
 // D = 16, 32, 64 in the CT form (4 DCs per lane), dense or MSK
 bool tags_serve_supported(const agn_log &log, bool sparse) {
     if (log.crdt_type == AGN_REGISTER_LWW) return false;  // k_lww: the batcher's sequence path
+    if (log.crdt_type == AGN_COUNTER_B) return false;     // k_bcounter: likewise
     const uint32_t D = log.n_dcs;
     if (D == 16 || D == 32 || D == 64) {  // the CT shapes, dense or MSK
         if (!tags_ct()) return false;
@@ -1074,6 +1070,7 @@ int launch_tags_serve_rest(const agn_log &log, const agn_read &req, const agn_re
 int launch_tags(const agn_log &log, const agn_read &req, const agn_result &out,
                 hipStream_t st, LwwOrder ord) {
     if (log.crdt_type == AGN_REGISTER_LWW) return launch_lww(log, req, out, st, ord);
+    if (log.crdt_type == AGN_COUNTER_B) return launch_bcounter(log, req, out, st);
     if (req.n_req == 0) return AGN_OK;
     // base_value without base_off names AGN_SS_STATE references into
     // base_tag / base_tok (ABI v4): both arrays are required for them

@@ -705,7 +705,7 @@ int agn_oplog_create(agn_ctx *ctx, uint32_t crdt_type, uint32_t n_dcs, uint64_t 
     *out = nullptr;
     if (n_dcs == 0 || n_dcs > 256) return fail(AGN_EINVAL, "oplog_create: n_dcs=%u", n_dcs);
     if (crdt_type != AGN_COUNTER_PN && crdt_type != AGN_SET_AW && crdt_type != AGN_REGISTER_MV &&
-        crdt_type != AGN_REGISTER_LWW)
+        crdt_type != AGN_REGISTER_LWW && crdt_type != AGN_COUNTER_B)
         return fail(AGN_EINVAL, "oplog_create: crdt_type %u", crdt_type);
     if (init_slots > (1u << 30)) return fail(AGN_EINVAL, "oplog_create: init_slots %u", init_slots);
     int rc = use_device(ctx);
@@ -820,9 +820,10 @@ static int oplog_append_locked(agn_oplog *L, uint64_t n, const uint64_t *keys,
                                uint32_t *out_op_id, uint8_t *out_gc_due) {
     if (!keys || !oc) return fail(AGN_EINVAL, "oplog_append: keys / oc required");
     if (L->sparse && !oc_mask) return fail(AGN_EINVAL, "oplog_append: sparse log needs oc_mask");
-    // register_lww entries remove nothing: rem_off may be NULL (all ranges empty)
+    // register_lww / counter_b entries remove nothing: rem_off may be NULL
+    // (all ranges empty)
     std::vector<uint32_t> no_rem;
-    if (L->crdt == AGN_REGISTER_LWW && !rem_off) {
+    if ((L->crdt == AGN_REGISTER_LWW || L->crdt == AGN_COUNTER_B) && !rem_off) {
         no_rem.assign(n + 1, 0u);
         rem_off = no_rem.data();
     }

@@ -79,6 +79,30 @@ def term_key(t):
     return (8, repr(t))
 
 
+def bcounter_slot(effect):
+    """counter_b update/2 effect -> (slot term, amount).  The slot is the
+    orddict key the effect adds to, P keys and D keys kept apart:
+      {{increment, V}, Id}        -> ("P", (Id, Id))
+      {{decrement, V}, Id}        -> ("D", Id)
+      {{transfer, V, ToId}, From} -> ("P", (From, ToId))
+    Any other shape, or V not an integer in [-2^63, 2^63 - 1], raises
+    ValueError (update/2's function_clause: an invalid entry)."""
+    if not (isinstance(effect, tuple) and len(effect) == 2 and isinstance(effect[0], tuple)):
+        raise ValueError(effect)
+    op, ident = effect
+    if len(op) == 2 and op[0] == "increment":
+        slot, v = ("P", (ident, ident)), op[1]
+    elif len(op) == 2 and op[0] == "decrement":
+        slot, v = ("D", ident), op[1]
+    elif len(op) == 3 and op[0] == "transfer":
+        slot, v = ("P", (ident, op[2])), op[1]
+    else:
+        raise ValueError(effect)
+    if not isinstance(v, int) or isinstance(v, bool) or not (-(1 << 63) <= v < (1 << 63)):
+        raise ValueError(effect)
+    return slot, v
+
+
 class DcTable(Interner):
     """dcid() -> column index."""
 
@@ -201,6 +225,9 @@ class LogEncoder:
                 if not isinstance(ts, int) or isinstance(ts, bool) or not (1 <= ts <= _abi.U64_MAX):
                     return None
                 return [(self.tags.id(value), ts, [])]
+            if t == _abi.COUNTER_B:
+                slot, amount = bcounter_slot(effect)
+                return [(self.tags.id(slot), amount & _abi.U64_MAX, [])]
         except (TypeError, ValueError):
             return None
         return None
@@ -341,6 +368,10 @@ class ReadEncoder:
                 for value_term, ts in (base or []):   # 0 or 1 pair: tok = the raw timestamp
                     btag.append(e.tags.id(value_term))
                     btok.append(int(ts))
+            elif e.crdt_type == _abi.COUNTER_B:
+                for slot_term, total in (base or []):   # tok = the sum, two's complement
+                    btag.append(e.tags.id(slot_term))
+                    btok.append(int(total) & _abi.U64_MAX)
             else:
                 for tag_term, toks in (base or []):
                     for tk in (toks if e.crdt_type == _abi.SET_AW else [toks]):
@@ -354,7 +385,8 @@ class ReadEncoder:
 
 def state_capacity(log: EncodedLog, req: EncodedRead) -> np.ndarray:
     """Upper bound of live pairs per request (adding entries + base pairs);
-    register_lww: 1 where the key has an entry or the request a base pair."""
+    register_lww: 1 where the key has an entry or the request a base pair;
+    counter_b: the key's entries (an amount of 0 is a value) + base pairs."""
     adds = (log.add_tok != 0).astype(np.uint64) if log.add_tok is not None else None
     cap = np.zeros(req.n_req + 1, np.uint64)
     for i, k in enumerate(req.keys):
@@ -364,6 +396,9 @@ def state_capacity(log: EncodedLog, req: EncodedRead) -> np.ndarray:
             if nb > 1:
                 raise ValueError(f"register_lww: request {i} has {nb} base pairs")
             cap[i + 1] = cap[i] + (1 if (b > a or nb) else 0)
+            continue
+        if log.crdt_type == _abi.COUNTER_B:
+            cap[i + 1] = cap[i] + (b - a) + int(req.base_off[i + 1] - req.base_off[i])
             continue
         c = int(adds[a:b].sum()) if adds is not None else 0
         c += int(req.base_off[i + 1] - req.base_off[i])

@@ -10,6 +10,7 @@ COUNTER_PN = "antidote_crdt_counter_pn"
 SET_AW = "antidote_crdt_set_aw"
 REGISTER_MV = "antidote_crdt_register_mv"
 REGISTER_LWW = "antidote_crdt_register_lww"
+COUNTER_B = "antidote_crdt_counter_b"
 FIRST_OP = 4  # include/antidote.hrl:90
 
 

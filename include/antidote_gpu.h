@@ -61,6 +61,10 @@ extern "C" {
 #define AGN_SET_AW 2       /* antidote_crdt_set_aw     */
 #define AGN_REGISTER_MV 3  /* antidote_crdt_register_mv */
 #define AGN_REGISTER_LWW 4 /* antidote_crdt_register_lww (addition to ABI v7) */
+/* 5 is reserved: every entry point refuses it ("unknown crdt_type 5") */
+#define AGN_COUNTER_B 6    /* antidote_crdt_counter_b (addition to ABI v7) */
+/* counter_b: the engine's per-key limit of distinct slots, base plus included */
+#define AGN_BCOUNTER_SLOTS_MAX 256
 #define AGN_TYPE_MIXED 0xFF /* key_type marker: the key's ops have different types */
 
 /* counter_pn effect that the Erlang side could not encode as an i64: applying
@@ -82,7 +86,10 @@ extern "C" {
  *   - the key needs more than 4096 candidate pairs at once in the engine's
  *     per-key table (live pairs plus a chunk's adds: the engine's own limit,
  *     whatever room the caller gave): out_n[i] is 0.
- * A request that ends in AGN_F_ERR_UNEXPECTED carries that error alone. */
+ * A request that ends in AGN_F_ERR_UNEXPECTED carries that error alone.
+ * counter_b has the same two causes: room smaller than the state (out_n[i] is
+ * the state's size) and more than AGN_BCOUNTER_SLOTS_MAX distinct slots, base
+ * plus included (out_n[i] is 0). */
 #define AGN_F_ERR_CAPACITY 0x10u  /* a per-key device table overflowed            */
 /* ABI v5: LastOpCt carries every column of the partition (its dict has all n_dcs
  * DCs); set only for requests of a batch with AGN_HINT_CT_FLAG, and then
@@ -127,6 +134,18 @@ extern "C" {
  *     2^64 - 1 included), compared unsigned.  In a base / result pair `tag` is
  *     the value id and `tok` the timestamp.  (A host encoder maps an effect
  *     that is not {integer Ts, V} with 1 <= Ts < 2^64 to an invalid entry.)
+ *   counter_b: tag[e] is the interned slot id -- an orddict key of the state
+ *     {P, D}: a P key {FromId, ToId} or a D key Id, interned apart -- any u32
+ *     but AGN_TAG_INVALID, which marks an effect the encoder could not
+ *     represent (not one of {{increment, V}, Id}, {{decrement, V}, Id},
+ *     {{transfer, V, To}, From}, or V not an integer in [-2^63, 2^63 - 1]);
+ *     add_tok[e] is the amount as two's complement, ANY u64 bit pattern, 0
+ *     included: the amount of a valid entry is never "none".  In a base /
+ *     result pair `tag` is the slot id and `tok` the sum's bits; a slot's sum
+ *     is the base sums plus the included amounts mod 2^64, as int64 (exact
+ *     whenever the true sum fits, counter_pn's convention).  A slot exists
+ *     once any applied effect named it, a sum of 0 included
+ *     (orddict:update_counter stores the key).
  *   op_id: any u32 but 0xFFFFFFFF (AGN_ID0_NONE, reserved by the id index);
  *     `hole` is the id zero-extended to int64, or id - 1.
  *   txid: any non-zero u64, 2^64 - 1 included; 0 means "none" in the log and
@@ -134,7 +153,7 @@ extern "C" {
 
 /* ---- op log (device or host pointers, same layout) -------------------- */
 typedef struct agn_log {
-    uint32_t crdt_type;       /* AGN_COUNTER_PN / AGN_SET_AW / AGN_REGISTER_MV / AGN_REGISTER_LWW */
+    uint32_t crdt_type;       /* AGN_COUNTER_PN / AGN_SET_AW / AGN_REGISTER_MV / AGN_REGISTER_LWW / AGN_COUNTER_B */
     uint32_t n_dcs;           /* D: vector-clock width */
     uint64_t n_keys;
     uint64_t n_entries;
@@ -173,6 +192,22 @@ typedef struct agn_log {
      * gives AGN_F_ERR_UNEXPECTED with err_pos the oldest such entry (out_n and
      * the pair are then unspecified); one live pair and no room gives
      * AGN_F_ERR_CAPACITY with out_n = 1. */
+    /* AGN_COUNTER_B: entry = one update/2 effect in the tag-type arrays: tag =
+     * slot id, add_tok = the amount (two's complement), no removals; rem_off
+     * follows register_lww's rules (may be NULL for agn_materialize and
+     * agn_oplog_append, REQUIRED and all zero for agn_prune_ops and
+     * agn_log_ingest).  This is the state clocksi_downstream:
+     * generate_downstream_op/6 reads for every bounded-counter write
+     * (src/clocksi_downstream.erl:61-64) and bcounter_mgr before each remote
+     * permission request (src/bcounter_mgr.erl:165-185).  The base state and
+     * the result use the pair layout, tok = the sum's bits; duplicate tags
+     * among the base pairs are summed; result pairs come out in ascending tag
+     * order, unsigned, each slot once; out_n == 0 means new() = {[], []};
+     * `value` is not written (permissions/1 is the host's sum over the pairs).
+     * A slot is present iff a base pair or an included entry with a valid tag
+     * names it.  An included entry with AGN_TAG_INVALID gives
+     * AGN_F_ERR_UNEXPECTED with err_pos the oldest such entry (out_n and the
+     * pairs are then unspecified).  AGN_F_ERR_CAPACITY: see the flag. */
     /* ABI v3, optional (NULL = read op_id): per key, the op id of the segment's
      * first entry when its ids are consecutive (op_id[off+p] == key_id0 + p
      * for every p < len), else AGN_ID0_NONE.  Ids stay consecutive from
@@ -442,7 +477,8 @@ int agn_log_index_eff16(agn_ctx *ctx, const agn_log *log, int16_t *eff16,
  * NULL -- must be host memory (copy a device agn_ss_lookup's base_value
  * back first).  AGN_REGISTER_LWW: cap = 1 where the key has an entry or the
  * request a base pair, else 0; a request with two or more base pairs is
- * AGN_EINVAL. */
+ * AGN_EINVAL.  AGN_COUNTER_B: cap = the key's entry count + the request's
+ * base pairs (every entry may name a slot of its own, whatever its amount). */
 int agn_state_capacity(const agn_log *host_log, const agn_read *host_req,
                        uint64_t *cap_off);
 
@@ -483,7 +519,8 @@ int agn_oplog_destroy(agn_oplog *log);
  * agn_ss_store(should_gc) + agn_oplog_prune) when it sees the flag.  oc[n][D] is the
  * OpSSCommit row (+ oc_mask[n][W] for a sparse log), txid may be NULL, the
  * effect arrays are those of the log's type, rem_off[n+1] is a CSR into
- * rem_tok (AGN_REGISTER_LWW: rem_off may be NULL, every range empty). */
+ * rem_tok (AGN_REGISTER_LWW / AGN_COUNTER_B: rem_off may be NULL, every range
+ * empty). */
 int agn_oplog_append(agn_oplog *log, uint64_t n, const uint64_t *keys, const uint8_t *same_op,
                      const uint64_t *oc, const uint64_t *oc_mask, const uint64_t *txid,
                      const int64_t *eff, const uint32_t *tag, const uint64_t *add_tok,

@@ -15,8 +15,8 @@
  *   one per vnode, holding keys of every CRDT type like ops_cache-<P>; one
  *   device op log per type, created with the type's first op; the resource's
  *   destructor frees them).  Type = a type atom (antidote_crdt_counter_pn,
- *   antidote_crdt_set_aw, antidote_crdt_register_mv, antidote_crdt_register_lww)
- *   or its id 1..4:
+ *   antidote_crdt_set_aw, antidote_crdt_register_mv, antidote_crdt_register_lww,
+ *   antidote_crdt_counter_b) or its id 1..4, 6 (5 is reserved and refused):
  *   part_open(Ctx, Type, NDcs, NKeys, Cached) -> {ok, Part}
  *       Type: the type whose log is created up front
  *   part_update(Part, Key, Type, OcPairs, TxId, Effect) -> {ok, OpId, GcDue}
@@ -24,7 +24,9 @@
  *       [{Dc, Time}] of the op's OpSSCommit, TxId a term or ignore, Effect the
  *       #clocksi_payload.op_param (counter_pn integer, set_aw
  *       [{Elem, AddToks, RemToks}], register_mv {V, Tok, Ovr} | {reset, Ovr},
- *       register_lww {Ts, V} with integer 1 =< Ts < 2^64)
+ *       register_lww {Ts, V} with integer 1 =< Ts < 2^64, counter_b
+ *       {{increment, V}, Id} | {{decrement, V}, Id} | {{transfer, V, To}, From}
+ *       with V an int64; its value is the state {P, D}, two orddicts)
  *   part_read(Part, Key, Type, RPairs, TxId, Gc) -> {ok, Value, NewLastOp,
  *       LastOpCt, IsNewSS, Count} | {error, no_snapshot} | {error, Reason}
  *       cached partition: the whole read/6 (device snapshot cache + GC);
@@ -106,7 +108,11 @@ typedef struct {
     int ready;              /* published (release) once every field is set */
 } part_sub;
 
-#define NTYPES 5 /* indexed by AGN_COUNTER_PN .. AGN_REGISTER_LWW */
+#define NTYPES 7 /* indexed by type id: AGN_COUNTER_PN .. AGN_REGISTER_LWW and
+                    AGN_COUNTER_B; slots 0 and 5 (reserved) stay empty */
+static int type_known(uint32_t t) {
+    return (t >= AGN_COUNTER_PN && t <= AGN_REGISTER_LWW) || t == AGN_COUNTER_B;
+}
 #define NO_HOME 0xFFu
 
 typedef struct {
@@ -158,6 +164,7 @@ static const char *type_name(uint32_t type) {
         case AGN_SET_AW: return "antidote_crdt_set_aw";
         case AGN_REGISTER_MV: return "antidote_crdt_register_mv";
         case AGN_REGISTER_LWW: return "antidote_crdt_register_lww";
+        case AGN_COUNTER_B: return "antidote_crdt_counter_b";
     }
     return "undefined";
 }
@@ -455,10 +462,10 @@ static int type_of(ErlNifEnv *env, ERL_NIF_TERM t, uint32_t *type) {
     unsigned v;
     if (enif_get_uint(env, t, &v)) {
         *type = v;
-        return v >= AGN_COUNTER_PN && v <= AGN_REGISTER_LWW;
+        return type_known(v);
     }
-    for (uint32_t x = AGN_COUNTER_PN; x <= AGN_REGISTER_LWW; ++x)
-        if (enif_is_identical(t, atom(env, type_name(x)))) {
+    for (uint32_t x = AGN_COUNTER_PN; x < NTYPES; ++x)
+        if (type_known(x) && enif_is_identical(t, atom(env, type_name(x)))) {
             *type = x;
             return 1;
         }
@@ -502,8 +509,8 @@ static int sub_make(part_res *p, uint32_t type, part_sub **out) {
  * type check over the key's ops, src/clocksi_materializer.erl:190-191)? */
 static int other_type_ops(part_res *p, uint64_t key, uint32_t type, int *out) {
     *out = 0;
-    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW && !*out; ++t) {
-        part_sub *s = t == type ? NULL : sub_get(p, t);
+    for (uint32_t t = AGN_COUNTER_PN; t < NTYPES && !*out; ++t) {
+        part_sub *s = (t == type || !type_known(t)) ? NULL : sub_get(p, t);
         uint32_t len = 0;
         if (!s) continue;
         int rc = agn_oplog_key_meta(s->log, 1, &key, &len, NULL, NULL);
@@ -726,6 +733,12 @@ static int push_entry(ErlNifEnv *env, part_res *p, entries *E, uint64_t tag, uin
     return 0;
 }
 
+/* counter_b: the slot term of an orddict key, {p, {From, To}} or {d, Id} */
+static ERL_NIF_TERM bc_slot(ErlNifEnv *env, int is_p, ERL_NIF_TERM from, ERL_NIF_TERM to) {
+    return is_p ? enif_make_tuple2(env, atom(env, "p"), enif_make_tuple2(env, from, to))
+                : enif_make_tuple2(env, atom(env, "d"), from);
+}
+
 static int effect_entries(ErlNifEnv *env, part_res *p, part_sub *sb, uint32_t type,
                           ERL_NIF_TERM eff, entries *E, int *err) {
     E->n = E->nrem = 0;
@@ -743,6 +756,30 @@ static int effect_entries(ErlNifEnv *env, part_res *p, part_sub *sb, uint32_t ty
         *err = lww_value_id(env, p, sb, tp[1], &id);
         if (*err) return -2;
         return push_entry(env, p, E, id, ts, NULL) ? -1 : 1;
+    }
+    if (type == AGN_COUNTER_B) {
+        /* {{increment, V}, Id} | {{decrement, V}, Id} | {{transfer, V, To}, From},
+         * V an int64: tag = the id of the orddict key the effect adds to ({p,
+         * {From, To}} or {d, Id}: P keys and D keys apart), add_tok = V as two's
+         * complement, nothing removed */
+        int oar;
+        const ERL_NIF_TERM *op;
+        ErlNifSInt64 v = 0;
+        uint64_t id = 0;
+        ERL_NIF_TERM slot;
+        if (!enif_get_tuple(env, eff, &ar, &tp) || ar != 2 || !enif_get_tuple(env, tp[0], &oar, &op) ||
+            oar < 2 || !enif_get_int64(env, op[1], &v))
+            return -1;
+        if (oar == 2 && enif_is_identical(op[0], atom(env, "increment")))
+            slot = bc_slot(env, 1, tp[1], tp[1]);
+        else if (oar == 2 && enif_is_identical(op[0], atom(env, "decrement")))
+            slot = bc_slot(env, 0, tp[1], tp[1]);
+        else if (oar == 3 && enif_is_identical(op[0], atom(env, "transfer")))
+            slot = bc_slot(env, 1, tp[1], op[2]);
+        else
+            return -1;
+        if (term_id(env, p->tags, slot, &id)) return -1;
+        return push_entry(env, p, E, id, (uint64_t)v, NULL) ? -1 : 1;
     }
     if (type == AGN_REGISTER_MV) {
         uint64_t tag = 0, tok = 0;
@@ -914,6 +951,59 @@ static ERL_NIF_TERM state_term(ErlNifEnv *env, part_res *p, uint32_t type, uint3
     return l;
 }
 
+/* counter_b: the result pairs -> the state {P, D}, two orddicts (sorted by
+ * enif_compare on the key: order is imposed after the fold, so the slot ids
+ * need no labels); 0 when out of memory */
+static ERL_NIF_TERM bc_state_term(ErlNifEnv *env, part_res *p, uint32_t n, const uint32_t *tag,
+                                  const uint64_t *tok) {
+    sort_item *v = enif_alloc(sizeof(sort_item) * (n + 1));
+    uint8_t *is_p = enif_alloc(n + 1);
+    if (!v || !is_p) {
+        enif_free(v);
+        enif_free(is_p);
+        return 0;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        int ar = 0;
+        const ERL_NIF_TERM *tp = NULL;
+        const ERL_NIF_TERM slot = id_term(env, p->tags, tag[i]);
+        if (!enif_get_tuple(env, slot, &ar, &tp) || ar != 2) {
+            v[i].key = slot;  /* not a slot term: cannot happen for the type's own log */
+            is_p[i] = 1;
+        } else {
+            v[i].key = tp[1];
+            is_p[i] = (uint8_t)enif_is_identical(tp[0], atom(env, "p"));
+        }
+        v[i].term = enif_make_tuple2(env, v[i].key, enif_make_int64(env, (ErlNifSInt64)tok[i]));
+    }
+    /* stable partition into P then D, each sorted by key */
+    sort_item *w = enif_alloc(sizeof(sort_item) * (n + 1));
+    if (!w) {
+        enif_free(v);
+        enif_free(is_p);
+        return 0;
+    }
+    uint32_t np = 0, nd = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (is_p[i]) w[np++] = v[i];
+    for (uint32_t i = 0; i < n; ++i)
+        if (!is_p[i]) w[np + nd++] = v[i];
+    qsort(w, np, sizeof *w, cmp_item);
+    qsort(w + np, nd, sizeof *w, cmp_item);
+    ERL_NIF_TERM P = enif_make_list(env, 0), D = enif_make_list(env, 0);
+    for (uint32_t i = np; i-- > 0;) P = enif_make_list_cell(env, w[i].term, P);
+    for (uint32_t i = np + nd; i-- > np;) D = enif_make_list_cell(env, w[i].term, D);
+    enif_free(v);
+    enif_free(w);
+    enif_free(is_p);
+    return enif_make_tuple2(env, P, D);
+}
+
+/* antidote_crdt_counter_b:new() = {[], []} */
+static ERL_NIF_TERM bc_new(ErlNifEnv *env) {
+    return enif_make_tuple2(env, enif_make_list(env, 0), enif_make_list(env, 0));
+}
+
 /* antidote_crdt_register_lww:new() = {0, <<>>} */
 static ERL_NIF_TERM lww_new(ErlNifEnv *env) {
     ERL_NIF_TERM b;
@@ -933,6 +1023,10 @@ static ERL_NIF_TERM read_result(ErlNifEnv *env, part_res *p, uint32_t type, uint
                                 enif_make_tuple3(env, atom(env, "unexpected_operation"),
                                                  inv_get(env, p, key, type, o->err_pos),
                                                  atom(env, type_name(type))));
+    /* counter_b: more than AGN_BCOUNTER_SLOTS_MAX distinct orddict keys (the
+     * room the NIF gives always holds the state, so this is the flag's one
+     * cause here): an error, never a truncated state */
+    if (type == AGN_COUNTER_B && (o->flags & AGN_F_ERR_CAPACITY)) return error_tuple(env, AGN_ECAPACITY);
     /* register_lww: two values tied at the winner's timestamp and one of them
      * has no label.  Every value is labelled before its op is appended, so
      * this is an internal error, never a value. */
@@ -944,6 +1038,7 @@ static ERL_NIF_TERM read_result(ErlNifEnv *env, part_res *p, uint32_t type, uint
         v = o->out_n ? enif_make_tuple2(env, enif_make_uint64(env, o->out_tok[0]),
                                         id_term(env, p->vals, o->out_tag[0]))
                      : lww_new(env);
+    else if (type == AGN_COUNTER_B) v = bc_state_term(env, p, o->out_n, o->out_tag, o->out_tok);
     else v = state_term(env, p, type, o->out_n, o->out_tag, o->out_tok);
     if (!v) return error_tuple(env, AGN_ENOMEM);
     ERL_NIF_TERM lct = (o->flags & AGN_F_CT_IGNORE) ? atom(env, "ignore") : clock_pairs(env, p, ct, ctm);
@@ -982,6 +1077,59 @@ static int state_pairs(ErlNifEnv *env, part_res *p, part_sub *sb, uint32_t type,
         tg[0] = (uint32_t)id;
         tk[0] = ts;
         *n_out = 1;
+        *tags_out = tg;
+        *toks_out = tk;
+        return AGN_OK;
+    }
+    if (type == AGN_COUNTER_B) {
+        /* {P, D}: one pair per orddict entry {Key, integer}, the slot terms of
+         * effect_entries */
+        int ar = 0;
+        const ERL_NIF_TERM *pd = NULL;
+        unsigned np = 0, nd = 0;
+        if (!enif_get_tuple(env, st, &ar, &pd) || ar != 2 || !enif_get_list_length(env, pd[0], &np) ||
+            !enif_get_list_length(env, pd[1], &nd))
+            return AGN_EINVAL;
+        if (np + nd == 0) return AGN_OK;
+        uint32_t *tg = enif_alloc(4 * (np + nd));
+        uint64_t *tk = enif_alloc(8 * (np + nd));
+        int rc = (!tg || !tk) ? AGN_ENOMEM : AGN_OK;
+        uint32_t n = 0;
+        for (int half = 0; half < 2 && !rc; ++half) {
+            ERL_NIF_TERM h, t = pd[half];
+            while (!rc && enif_get_list_cell(env, t, &h, &t)) {
+                int kar = 0;
+                const ERL_NIF_TERM *kv = NULL, *ft = NULL;
+                ErlNifSInt64 v = 0;
+                uint64_t id = 0;
+                if (!enif_get_tuple(env, h, &kar, &kv) || kar != 2 || !enif_get_int64(env, kv[1], &v)) {
+                    rc = AGN_EINVAL;
+                    break;
+                }
+                ERL_NIF_TERM slot;
+                if (half == 0) {
+                    int far = 0;
+                    if (!enif_get_tuple(env, kv[0], &far, &ft) || far != 2) {
+                        rc = AGN_EINVAL;
+                        break;
+                    }
+                    slot = bc_slot(env, 1, ft[0], ft[1]);
+                } else {
+                    slot = bc_slot(env, 0, kv[0], kv[0]);
+                }
+                rc = term_id(env, p->tags, slot, &id);
+                if (!rc) {
+                    tg[n] = (uint32_t)id;
+                    tk[n++] = (uint64_t)v;
+                }
+            }
+        }
+        if (rc) {
+            enif_free(tg);
+            enif_free(tk);
+            return rc;
+        }
+        *n_out = n;
         *tags_out = tg;
         *toks_out = tk;
         return AGN_OK;
@@ -1076,6 +1224,8 @@ static ERL_NIF_TERM part_read_common(ErlNifEnv *env, part_res *p, ERL_NIF_TERM k
                     ? enif_make_int64(env, b) : enif_make_int64(env, 0);
         else if (type == AGN_REGISTER_LWW)
             v = (!p->cached && enif_get_tuple(env, base, &lar, &ltp) && lar == 2) ? base : lww_new(env);
+        else if (type == AGN_COUNTER_B)
+            v = (!p->cached && enif_get_tuple(env, base, &lar, &ltp) && lar == 2) ? base : bc_new(env);
         else
             v = (!p->cached && enif_is_list(env, base)) ? base : enif_make_list(env, 0);
         ERL_NIF_TERM res[6] = {atom(env, "ok"), v, enif_make_int64(env, 0),
@@ -1250,8 +1400,8 @@ static ERL_NIF_TERM nif_part_gc(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
     agn_ctx *c = p->ctx->ctx;
     const uint8_t one = 1;
     pthread_mutex_lock(&p->gc_mu);
-    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW && !rc; ++t) {
-        part_sub *s = sub_get(p, t);
+    for (uint32_t t = AGN_COUNTER_PN; t < NTYPES && !rc; ++t) {
+        part_sub *s = type_known(t) ? sub_get(p, t) : NULL;
         uint32_t len = 0;
         if (!s) continue;
         rc = agn_oplog_key_meta(s->log, 1, &k, &len, NULL, NULL);
@@ -1287,8 +1437,8 @@ static ERL_NIF_TERM nif_part_gc_due(ErlNifEnv *env, int argc, const ERL_NIF_TERM
     uint8_t due = 0;
     if (p->khome[k] != NO_HOME) {
         uint32_t total = 0, lcap = 0;
-        for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW && !rc; ++t) {
-            part_sub *s = sub_get(p, t);
+        for (uint32_t t = AGN_COUNTER_PN; t < NTYPES && !rc; ++t) {
+            part_sub *s = type_known(t) ? sub_get(p, t) : NULL;
             uint32_t len = 0, ll = 0;
             if (!s) continue;
             rc = agn_oplog_key_meta(s->log, 1, &k, &len, &ll, NULL);
@@ -1306,8 +1456,8 @@ static ERL_NIF_TERM nif_part_stats(ErlNifEnv *env, int argc, const ERL_NIF_TERM 
     part_res *p;
     uint64_t E = 0, S = 0, T = 0;
     if (argc != 1 || !get_part(env, argv[0], &p)) return enif_make_badarg(env);
-    for (uint32_t t = AGN_COUNTER_PN; t <= AGN_REGISTER_LWW; ++t) {
-        part_sub *s = sub_get(p, t);
+    for (uint32_t t = AGN_COUNTER_PN; t < NTYPES; ++t) {
+        part_sub *s = type_known(t) ? sub_get(p, t) : NULL;
         uint64_t e, sl, tk;
         if (!s) continue;
         int rc = agn_oplog_stats(s->log, &e, &sl, &tk);

@@ -28,10 +28,14 @@
 -define(SET_AW, 2).
 -define(REGISTER_MV, 3).
 -define(REGISTER_LWW, 4).
+-define(COUNTER_B, 6).   % 5 is reserved: the engine refuses it
+-define(I64_MIN, -16#8000000000000000).
+-define(I64_MAX, 16#7FFFFFFFFFFFFFFF).
 -define(F_NEWSS, 1).
 -define(F_CT_IGNORE, 2).
 -define(F_ERR_UNEXPECTED, 4).
 -define(F_ERR_CORRUPTED, 8).
+-define(F_ERR_CAPACITY, 16#10).
 -define(INVALID_EFFECT, -16#8000000000000000).
 -define(U64_MAX, 16#FFFFFFFFFFFFFFFF).
 
@@ -68,7 +72,8 @@ ctx() ->
 type_id(antidote_crdt_counter_pn) -> ?COUNTER;
 type_id(antidote_crdt_set_aw) -> ?SET_AW;
 type_id(antidote_crdt_register_mv) -> ?REGISTER_MV;
-type_id(antidote_crdt_register_lww) -> ?REGISTER_LWW.
+type_id(antidote_crdt_register_lww) -> ?REGISTER_LWW;
+type_id(antidote_crdt_counter_b) -> ?COUNTER_B.
 
 %% ---------------------------------------------------------------------------
 %% clocksi_materializer:materialize/4, same arguments and results.
@@ -251,6 +256,14 @@ parts(?REGISTER_MV, {reset, Ovr}) when is_list(Ovr) -> {ok, [{reset, none, Ovr}]
 parts(?REGISTER_MV, {Value, Token, Ovr}) when is_list(Ovr) -> {ok, [{Value, Token, Ovr}]};
 parts(?REGISTER_LWW, {Ts, Value}) when is_integer(Ts), Ts >= 1, Ts =< ?U64_MAX ->
     {ok, [{Value, {raw, Ts}, []}]};
+%% counter_b update/2: the orddict key the effect adds to ({p, {From, To}} or
+%% {d, Id}: P keys and D keys apart) and the amount raw, as two's complement
+parts(?COUNTER_B, {{increment, V}, Id}) when is_integer(V), V >= ?I64_MIN, V =< ?I64_MAX ->
+    {ok, [{{p, {Id, Id}}, {raw, V}, []}]};
+parts(?COUNTER_B, {{decrement, V}, Id}) when is_integer(V), V >= ?I64_MIN, V =< ?I64_MAX ->
+    {ok, [{{d, Id}, {raw, V}, []}]};
+parts(?COUNTER_B, {{transfer, V, ToId}, FromId}) when is_integer(V), V >= ?I64_MIN, V =< ?I64_MAX ->
+    {ok, [{{p, {FromId, ToId}}, {raw, V}, []}]};
 parts(_, _) -> error.
 
 set_part({Elem, [], Rems}) when is_list(Rems) -> [{Elem, none, Rems}];
@@ -269,6 +282,15 @@ encode_base(?REGISTER_LWW, {0, _}, Tags, Toks) ->       % new() = {0, <<>>}: no 
 encode_base(?REGISTER_LWW, {Ts, Value}, Tags, Toks) ->  % interned with the log's values
     {<<0:64/native, 1:64/native>>, <<(maps:get(Value, Tags)):32/native>>, <<Ts:64/native>>,
      Tags, Toks};
+encode_base(?COUNTER_B, {P, D}, Tags, Toks) ->          % {P, D}: one pair per orddict entry
+    Pairs = [{{p, K}, V} || {K, V} <- P] ++ [{{d, K}, V} || {K, V} <- D],
+    {TagB, TokB, Tags1} = lists:foldl(
+        fun({Slot, V}, {TgA, TkA, Tg}) ->
+                {Tg1, TagId} = intern(Slot, Tg),
+                {[<<TagId:32/native>> | TgA], [<<V:64/signed-native>> | TkA], Tg1}
+        end, {[], [], Tags}, Pairs),
+    {<<0:64/native, (length(Pairs)):64/native>>, iolist_to_binary(lists:reverse(TagB)),
+     iolist_to_binary(lists:reverse(TokB)), Tags1, Toks};
 encode_base(_, _, Tags, Toks) ->
     {<<>>, <<>>, <<>>, Tags, Toks}.
 
@@ -316,6 +338,10 @@ decode(Type, TypeId, Dcs, D, {Value, Hole, LastCt, LastCtMask, Count, Flags, Err
         F band ?F_ERR_UNEXPECTED =/= 0 ->
             <<E:32/native>> = ErrPos,
             {error, {unexpected_operation, maps:get(E, Terms, undefined), Type}};
+        %% counter_b: more than AGN_BCOUNTER_SLOTS_MAX distinct orddict keys (the
+        %% room encode_read/9 gives always holds the state, so this is the
+        %% flag's one cause here; out_n is 0 then): an error, never new()
+        F band ?F_ERR_CAPACITY =/= 0, TypeId =:= ?COUNTER_B -> {error, ecapacity};
         true ->
             Ct = case F band ?F_CT_IGNORE of
                      0 -> decode_clock(Dcs, D, LastCt, LastCtMask);
@@ -324,6 +350,7 @@ decode(Type, TypeId, Dcs, D, {Value, Hole, LastCt, LastCtMask, Count, Flags, Err
             V = case TypeId of
                     ?COUNTER -> <<X:64/signed-native>> = Value, X;
                     ?REGISTER_LWW -> decode_lww(OutN, OutTag, OutTok, Tags);
+                    ?COUNTER_B -> decode_bcounter(OutN, OutTag, OutTok, Tags);
                     _ -> decode_state(TypeId, OutN, OutTag, OutTok, Tags, Toks)
                 end,
             {ok, V, H, Ct, F band ?F_NEWSS =/= 0, C}
@@ -335,6 +362,15 @@ decode_clock(Dcs, D, Vals, MaskBin) ->
     L = [V || <<V:64/native>> <= Vals],
     dict:from_list([{Dc, lists:nth(I + 1, L)} || {Dc, I} <- lists:zip(Dcs, lists:seq(0, length(Dcs) - 1)),
                                                  (Mask bsr I) band 1 =:= 1]).
+
+%% counter_b: the result pairs -> {P, D}, two orddicts (out_n = 0: new())
+decode_bcounter(<<N:32/native>>, TagBin, TokBin, Tags) ->
+    RTags = maps:from_list([{I, T} || {T, I} <- maps:to_list(Tags)]),
+    Pairs = lists:sublist(lists:zip([T || <<T:32/native>> <= TagBin],
+                                    [V || <<V:64/signed-native>> <= TokBin]), N),
+    Slots = [{maps:get(T, RTags), V} || {T, V} <- Pairs],
+    {orddict:from_list([{K, V} || {{p, K}, V} <- Slots]),
+     orddict:from_list([{K, V} || {{d, K}, V} <- Slots])}.
 
 decode_state(TypeId, <<N:32/native>>, TagBin, TokBin, Tags, Toks) ->
     RTags = maps:from_list([{I, T} || {T, I} <- maps:to_list(Tags)]),
