@@ -1202,13 +1202,13 @@ static int read_cached_tags(agn_ss_cache *cache, const agn_log *log, uint64_t n_
     return rc;
 }
 
-// read/6 of a register_lww batch, D <= 64: the one fused launch
-// (tags_serve.hpp, k_lww_serve) over the caller's device arrays.  No GC list
-// and no deltas: the device state_ctl is authoritative.
-static int read_cached_lww(agn_ss_cache *cache, const agn_log *log, uint64_t n_req,
-                           const uint64_t *keys, const uint64_t *R, const uint64_t *txid,
-                           const uint8_t *should_gc, agn_result *out, uint8_t *status,
-                           uint8_t *prune, uint64_t *threshold, hipStream_t st) {
+// read/6 of a register_lww or counter_b batch, D <= 64: the one fused launch
+// (tags_serve.hpp, k_lww_serve / k_bcounter_serve) over the caller's device
+// arrays.  No GC list and no deltas: the device state_ctl is authoritative.
+static int read_cached_serve(agn_ss_cache *cache, const agn_log *log, uint64_t n_req,
+                             const uint64_t *keys, const uint64_t *R, const uint64_t *txid,
+                             const uint8_t *should_gc, agn_result *out, uint8_t *status,
+                             uint8_t *prune, uint64_t *threshold, hipStream_t st) {
     const uint32_t D = log->n_dcs;
     uint8_t *tmp = nullptr;  // sct [n][D] u64 | base [n] i64 | ign [n] | first [n]
     AGN_HIP(pool_malloc((void **)&tmp, n_req * (8ull * D + 8ull + 2ull), st));
@@ -1236,7 +1236,8 @@ static int read_cached_lww(agn_ss_cache *cache, const agn_log *log, uint64_t n_r
     rq.base_value = sv.base;  // AGN_SS_STATE references into the arena
     rq.base_tag = cache->state_tag;
     rq.base_tok = cache->state_tok;
-    const int rc = launch_lww_serve(*log, rq, o, sv, st);
+    const int rc = log->crdt_type == AGN_COUNTER_B ? launch_bcounter_serve(*log, rq, o, sv, st)
+                                                   : launch_lww_serve(*log, rq, o, sv, st);
     (void)hipFreeAsync(tmp, st);
     return rc;
 }
@@ -1249,14 +1250,36 @@ static int read_cached_lww(agn_ss_cache *cache, const agn_log *log, uint64_t n_r
 // 45.8), 16384 59.5 vs 51.2 (49.4 to 52.4), 2^15 105 vs 80, 2^20 3.37 vs 2.17
 // ms -- the batched lookup and store serve 8 requests per wave.  Measured at
 // D = 8 only; the one value holds for every D <= 64.
-// AGN_READ_CACHED_SPLIT=<n> moves this switch too (0: never).
-static uint64_t read_cached_lww_split() {
+static const uint64_t READ_CACHED_LWW_SPLIT = 1ull << 14;
+
+// counter_b's agn_read_cached batch size from which the kernel sequence runs
+// instead of the fused launch (AGN_BCOUNTER_FUSED=1 only): 12288 requests, the
+// smallest measured size from which the fused median lies on the slow side of
+// the sequence's own min ... max range.  D = 8, generator keys of 64 ops over 4
+// slots, hits that store nothing, fused vs sequence (min ... max), medians of
+// 15 rounds (scripts/ab_bcounter_serve.py,
+// profiles/bcounter_serve/ab_bcounter_serve*.json):
+//    2048   19.0 vs  25.6 us (25.2 ... 37.4)
+//    4096   27.0 vs  28.2    (27.8 ... 37.2)
+//    6144   32.6 vs  35.9    (34.7 ... 49.0)
+//    8192   42.1 vs  39.0    (38.3 ... 45.2)   inside the range
+//   12288   54.2 vs  46.0    (45.4 ... 49.9)   behind it, and so from here on
+//   16384   70.2 vs  54.3    (53.5 ... 57.9)
+//   32768  123.8 vs  83.2    (82.2 ... 87.6)
+//    2^20   3.96 vs  2.39 ms (9 rounds)
+// -- the batched lookup and store serve 8 requests per wave.  Measured at
+// D = 8 only; the one value holds for every D <= 64.
+static const uint64_t READ_CACHED_BCOUNTER_SPLIT = 12288ull;
+
+// The serve kernels' switch: the type's measured size above, or
+// AGN_READ_CACHED_SPLIT=<n>, which moves these switches too (0: never).
+static uint64_t read_cached_serve_split(uint64_t measured) {
     const char *v = AGN_KNOB("AGN_READ_CACHED_SPLIT");
     if (v && v[0]) {
         const uint64_t n = strtoull(v, nullptr, 10);
         return n ? n : ~0ull;
     }
-    return 1ull << 14;
+    return measured;
 }
 
 int agn_read_cached_path(const agn_ss_cache *cache, const agn_log *log, uint64_t n_req,
@@ -1273,7 +1296,10 @@ int agn_read_cached_path(const agn_ss_cache *cache, const agn_log *log, uint64_t
                                      "arena and dense clocks");
         if (log->crdt_type == AGN_REGISTER_LWW && lww_serve_supported(*log, false)) {
             const char *v = AGN_KNOB("AGN_LWW_FUSED");
-            *fused = !(v && v[0] == '0') && n_req < read_cached_lww_split();
+            *fused = !(v && v[0] == '0') && n_req < read_cached_serve_split(READ_CACHED_LWW_SPLIT);
+        } else if (log->crdt_type == AGN_COUNTER_B && bcounter_serve_supported(*log, false)) {
+            const char *v = AGN_KNOB("AGN_BCOUNTER_FUSED");
+            *fused = v && v[0] == '1' && n_req < read_cached_serve_split(READ_CACHED_BCOUNTER_SPLIT);
         }
         return AGN_OK;
     }
@@ -1330,8 +1356,8 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
         rc = use_device(ctx);
         if (rc) return rc;
         if (fused)
-            return read_cached_lww(cache, log, n_req, keys, R, txid, should_gc, out, status,
-                                   prune, threshold, (hipStream_t)stream);
+            return read_cached_serve(cache, log, n_req, keys, R, txid, should_gc, out, status,
+                                     prune, threshold, (hipStream_t)stream);
         return read_cached_tags(cache, log, n_req, keys, R, txid, should_gc, out, status, prune,
                                 threshold, (hipStream_t)stream);
     }

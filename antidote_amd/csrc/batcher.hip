@@ -96,6 +96,7 @@ struct agn_batcher {
     bool read6 = true;  // the fused one-kernel batch (AGN_READ6=0: the kernel sequence)
     bool tags_fused = true;  // set/register batches too (AGN_TAGS_FUSED=0: their sequence)
     bool lww_fused = true;   // register_lww's fused kernel (AGN_LWW_FUSED=0: its sequence alone)
+    bool bcounter_fused = false;  // counter_b's fused kernel (AGN_BCOUNTER_FUSED=1; off: its sequence)
     // agn_batcher_path_stats: batches served by one fused launch / any other way
     std::atomic<uint64_t> n_fused{0}, n_sequence{0};
     bool one_launch = false;  // the running batch (worker only): set by the fused paths
@@ -354,9 +355,12 @@ int ensure_state_room(agn_batcher *B, uint64_t need) {
 // from the stores' reported deltas.  A batch with keys the kernel handed on
 // (a state past the fast table, a key not uniform inside R's DC set) runs
 // the remaining passes and their store, and reads state_ctl back.
-// lww: register_lww's kernel (k_lww_serve, D <= 64) over the same blocks; it
-// hands nothing on and needs no scratch words.
-int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse, bool lww) {
+// SERVE_LWW / SERVE_BCOUNTER: register_lww's kernel (k_lww_serve) and
+// counter_b's (k_bcounter_serve), D <= 64, over the same blocks; they hand
+// nothing on and need no scratch words.
+enum ServeKernel { SERVE_TAGS, SERVE_LWW, SERVE_BCOUNTER };
+int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse, ServeKernel sk) {
+    const bool tags = sk == SERVE_TAGS;
     const uint64_t n = b.size();
     const uint32_t D = B->D, W = B->W;
     std::vector<uint64_t> keys(n);
@@ -373,7 +377,7 @@ int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse,
         const uint64_t ncap = co[n];
         rc = ensure_state_room(B, ncap);
         if (rc) return rc;
-        if (!lww && B->tscr_n < n) {
+        if (tags && B->tscr_n < n) {
             const uint64_t m = std::max<uint64_t>(n, 2 * B->tscr_n);
             if (B->tscr) AGN_HIP(hipFree(B->tscr));
             B->tscr = nullptr;
@@ -460,13 +464,14 @@ int run_batch_tags_fused(agn_batcher *B, std::vector<Pending *> &b, bool sparse,
         sv.dprune = (uint8_t *)(d + d_pr);
         sv.thr = B->thr;
         sv.thrm = B->thrm;
-        rc = lww ? launch_lww_serve(view, req, res, sv, B->stream, oplog_lww_order(B->log))
-                 : launch_tags_serve(view, req, res, sv, B->tscr, B->stream);
+        rc = sk == SERVE_LWW ? launch_lww_serve(view, req, res, sv, B->stream, oplog_lww_order(B->log))
+             : sk == SERVE_BCOUNTER ? launch_bcounter_serve(view, req, res, sv, B->stream)
+                                    : launch_tags_serve(view, req, res, sv, B->tscr, B->stream);
         if (rc) return rc;
         rc = wait_batch(B);
         if (rc) return rc;
         bool handed_on = false;
-        for (uint64_t i = 0; !lww && i < n; ++i)
+        for (uint64_t i = 0; tags && i < n; ++i)
             handed_on = handed_on || (((const uint8_t *)H(o_pr))[i] & 4u);
         B->one_launch = !handed_on;
         if (handed_on) {
@@ -542,9 +547,11 @@ int run_batch_cached_tags(agn_batcher *B, std::vector<Pending *> &b) {
         v.n_dcs = D;
         v.crdt_type = B->crdt;
         if (lww_serve_supported(v, sparse)) {
-            if (B->lww_fused) return run_batch_tags_fused(B, b, sparse, true);
+            if (B->lww_fused) return run_batch_tags_fused(B, b, sparse, SERVE_LWW);
+        } else if (bcounter_serve_supported(v, sparse)) {
+            if (B->bcounter_fused) return run_batch_tags_fused(B, b, sparse, SERVE_BCOUNTER);
         } else if (tags_serve_supported(v, sparse)) {
-            return run_batch_tags_fused(B, b, sparse, false);
+            return run_batch_tags_fused(B, b, sparse, SERVE_TAGS);
         }
     }
     std::vector<uint64_t> keys(n);
@@ -1244,6 +1251,8 @@ int agn_batcher_create_cached(agn_oplog *log, uint32_t slots, uint32_t max_batch
     (*out)->tags_fused = !(tf && tf[0] == '0');
     const char *lf = AGN_KNOB("AGN_LWW_FUSED");
     (*out)->lww_fused = !(lf && lf[0] == '0');
+    const char *bf = AGN_KNOB("AGN_BCOUNTER_FUSED");
+    (*out)->bcounter_fused = bf && bf[0] == '1';
     (*out)->ss = c;
     (*out)->thr = thr;
     (*out)->thrm = thrm;

@@ -52,6 +52,18 @@ bool lww_serve_supported(const agn_log &shape, bool sparse);
 int launch_lww_serve(const agn_log &log, const agn_read &req, const agn_result &out,
                      const TagServe &sv, hipStream_t st, LwwOrder ord = LwwOrder());
 
+// The fused counter_b cached read (mat_bcounter.hip, k_bcounter_serve): lookup
+// -> k_bcounter's fold from the hit slot's pairs in the arena -> store of the
+// result's pairs in ascending tag order, one wave per request, one launch per
+// batch.  A state is at most AGN_BCOUNTER_SLOTS_MAX pairs, held in the wave's
+// LDS table, so no request is handed on: no scratch words, no _rest, and
+// prune[i] never carries 4.  Shapes and the optional sv members: as
+// launch_lww_serve.  Selected by AGN_BCOUNTER_FUSED=1 (batcher.hip, api.hip);
+// tags_serve_supported stays false for the type.
+bool bcounter_serve_supported(const agn_log &shape, bool sparse);
+int launch_bcounter_serve(const agn_log &log, const agn_read &req, const agn_result &out,
+                          const TagServe &sv, hipStream_t st);
+
 // agn_ss_store (prune flags per request) over a device list of request
 // indices list[0, *list_n) (cache.hip).
 int launch_ss_store_list(const agn_ss_cache &c, const uint64_t *key_off, const uint64_t *key_len,

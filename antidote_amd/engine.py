@@ -237,7 +237,10 @@ class Engine:
                     status_ptr, prune_ptr, thr_ptr, stream=None):
         """agn_read_cached: read/6 for a batch in one kernel (ss_lookup ->
         materialize -> ss_store): counter_pn with dense clocks, D <= 8, and
-        register_lww with a state arena, D <= 64 (read_cached_path tells)."""
+        register_lww with a state arena, D <= 64 (read_cached_path tells).
+        counter_b with a state arena, D <= 64, takes one fused launch only
+        with AGN_BCOUNTER_FUSED=1 in the environment (off by default: the
+        kernel sequence; same results either way)."""
         ls = dlog.struct if isinstance(dlog, DeviceArrays) else dlog
         rs = dres.struct if isinstance(dres, DeviceArrays) else dres
         check(self.lib.agn_read_cached(self.ctx, C.byref(cache), C.byref(ls), n_req, keys_ptr,
@@ -521,7 +524,11 @@ class Batcher:
     def __init__(self, oplog: OpLog, max_batch: int = 1024, max_wait_us: int = 0,
                  cached: bool = False, slots: int = 0):
         """cached=True: agn_batcher_create_cached -- each batch is the whole
-        read/6 over the batcher's device snapshot cache (counter_pn)."""
+        read/6 over the batcher's device snapshot cache (counter_pn).  The
+        A/B knobs are read here, when the batcher is created: AGN_READ6,
+        AGN_TAGS_FUSED, AGN_LWW_FUSED (0: that type's kernel sequence) and
+        AGN_BCOUNTER_FUSED (1: counter_b batches at D <= 64 run the fused
+        k_bcounter_serve; unset or 0, the default, their kernel sequence)."""
         self.oplog, self.lib = oplog, oplog.eng.lib
         self.h = C.c_void_p()
         if cached:
@@ -581,7 +588,8 @@ class Batcher:
 
     def path_stats(self):
         """agn_batcher_path_stats: batches served by one fused launch, and
-        batches served any other way."""
+        batches served any other way.  A counter_b batcher reports fused
+        batches only when it was created with AGN_BCOUNTER_FUSED=1."""
         f, s = C.c_uint64(), C.c_uint64()
         check(self.lib.agn_batcher_path_stats(self.h, C.byref(f), C.byref(s)),
               "agn_batcher_path_stats")

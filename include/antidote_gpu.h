@@ -898,6 +898,17 @@ int agn_read_cached(agn_ctx *ctx, agn_ss_cache *cache, const agn_log *log, uint6
  * beyond 64 DCs, or with AGN_LWW_FUSED=0, the three batched kernels.  Same
  * results either way.
  *
+ * counter_b: AGN_BCOUNTER_FUSED=1 serves a counter_b log over such a cache
+ * (state arena, dense clocks, D <= 64) in one fused launch too
+ * (k_bcounter_serve: lookup -> the slot-sum fold from the hit snapshot's pairs
+ * in the arena -> store of the result's pairs in ascending tag order, one wave
+ * per request; nothing is handed on), below 12288 requests
+ * (AGN_READ_CACHED_SPLIT moves this switch as well).  Unset or 0 -- the
+ * default -- keeps the three batched kernels at every size: the knob is off
+ * until the default is flipped on the measurements of DESIGN.md 4.6f.  Same
+ * results either way.  The read batcher (agn_batcher_create_cached) reads the
+ * same knob when it is created.
+ *
  * agn_read_cached_path: host-only, touches no device.  *fused = 1 when
  * agn_read_cached would serve these arguments in one launch, 0 for the
  * batched kernels; AGN_EINVAL / AGN_ENOTSUP as agn_read_cached's validation

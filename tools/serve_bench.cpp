@@ -26,9 +26,12 @@
 // previous token of it, as the CRDTs' downstream does): their snapshot states
 // live in the cache's device arena.  type=lww serves register_lww partitions:
 // one {Ts, V} entry per op, no removals, a key's timestamps increasing with an
-// occasional repeat (a tie).
+// occasional repeat (a tie).  type=bcounter serves counter_b partitions: one
+// (slot, amount) effect per op over 4 slots per key, signed amounts, no
+// removals; a read's result is the key's (slot, sum) pairs
+// (AGN_BCOUNTER_FUSED=1 selects the fused kernel for them).
 //
-//   serve_bench [type=counter|set|register|lww] [keys=N] [ops=N] [dcs=N] [present=N]
+//   serve_bench [type=counter|set|register|lww|bcounter] [keys=N] [ops=N] [dcs=N] [present=N]
 //               [sparse=0|1] [parts=N] [threads=N] [reads=N] [batch=N] [wait=US]
 //               [wps=N] [hot=N] [crash=1]
 #include <dlfcn.h>
@@ -152,6 +155,7 @@ struct Partition {
 };
 
 constexpr uint64_t NE = 16;  // set elements / register values per key
+constexpr uint64_t NB = 4;   // counter_b slots per key
 
 // One set/register effect of key k (writer state in pt): tag, add token and
 // the tokens it removes / overrides.
@@ -159,6 +163,13 @@ void tag_effect(Partition &pt, uint32_t crdt, uint64_t k, uint64_t &seed, uint32
                 uint64_t &add, std::vector<uint64_t> &rems) {
     const uint64_t e = splitmix(seed) % NE;
     tag = (uint32_t)e;
+    if (crdt == AGN_COUNTER_B) {
+        // a slot of the key's four and a signed amount, as generate_downstream
+        // leaves increments, decrements and transfers
+        tag = (uint32_t)(e % NB);
+        add = (uint64_t)((int64_t)(splitmix(seed) % 21) - 10);
+        return;
+    }
     if (crdt == AGN_REGISTER_LWW) {
         // one {Ts, V} entry, no removals: the key's timestamps increase, now
         // and then one repeats (a tie when its value differs)
@@ -205,8 +216,10 @@ int main(int argc, char **argv) {
         else if (k == "type") {
             const std::string t = v;
             crdt = t == "set" ? AGN_SET_AW : t == "register" ? AGN_REGISTER_MV
-                 : t == "lww" ? AGN_REGISTER_LWW : AGN_COUNTER_PN;
-            if (t != "set" && t != "register" && t != "lww" && t != "counter") return 2;
+                 : t == "lww" ? AGN_REGISTER_LWW : t == "bcounter" ? AGN_COUNTER_B
+                 : AGN_COUNTER_PN;
+            if (t != "set" && t != "register" && t != "lww" && t != "bcounter" && t != "counter")
+                return 2;
         }
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -429,7 +442,8 @@ int main(int argc, char **argv) {
         "\"batches\": %llu, \"mean_batch\": %.2f, \"status\": {\"hit\": %llu, \"new\": %llu, "
         "\"log\": %llu}, \"errors\": %llu, \"fused_batches\": %llu}\n",
         crdt == AGN_SET_AW ? "set_aw" : crdt == AGN_REGISTER_MV ? "register_mv"
-        : crdt == AGN_REGISTER_LWW ? "register_lww" : "counter_pn",
+        : crdt == AGN_REGISTER_LWW ? "register_lww" : crdt == AGN_COUNTER_B ? "counter_b"
+        : "counter_pn",
         sparse ? "sparse (presence masks, as the NIF builds it)" : "dense", (unsigned long long)present,
         (unsigned long long)P, (unsigned long long)K, (unsigned long long)H, (unsigned long long)N,
         (unsigned long long)D, (unsigned long long)T, (unsigned long long)reads,
